@@ -12,6 +12,13 @@ no collective on the data path (weak scaling: every rank owns its own
 4096-stripe batch); gloo is used only for the barrier and the max-over-ranks
 timing reduction.
 
+A plain run sets up, warms up, times --steps steps, writes the last step's
+outputs if --dump-outputs DIR is given and prints the line (value,
+ms_per_step, the event-timed roofline of the timed launches).  --full adds
+every leg with runs of its own: the checksum and erase-and-rebuild
+verification, the on-device copy ceiling, the host-inclusive legs, the drop-in
+pool rate and the CPU baselines.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -46,6 +53,14 @@ def parse(argv=None):
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--chunk", type=int, default=1 << 20)
     ap.add_argument("--stripes", type=int, default=4096, help="stripes per GPU (batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure also run what takes runs of its own: the checksum and "
+                         "erase-and-rebuild verification, the on-device copy ceiling, the host-inclusive legs, the "
+                         "drop-in pool rate and the CPU baselines (a plain run only sets up, warms up, times the "
+                         "steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float32; a "
+                         "fixed, seeded sample of outputs larger than the dump budget)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (default: every CPU of this process's affinity mask)")
@@ -53,7 +68,8 @@ def parse(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=3.0, help="min wall time of the SIMD CPU baseline leg")
     ap.add_argument("--cpu-ref-stripes", type=int, default=96, help="stripes for the (slow) reference base-C leg")
     ap.add_argument("--host-inclusive", dest="host_inclusive", action="store_true", default=True,
-                    help="also time the pinned H2D->encode->D2H pipeline (default on; N=1 headline workload only)")
+                    help="with --full: also time the pinned H2D->encode->D2H pipeline (default on; N=1 headline "
+                         "workload only)")
     ap.add_argument("--no-host-inclusive", dest="host_inclusive", action="store_false")
     ap.add_argument("--workload", choices=sorted(["rs10_4", "decode_full", "repair12", "mixed16", "write14", "object",
                                                  "files", "config1"]), default="rs10_4",
@@ -290,6 +306,62 @@ class Workload:
         self.erase = erase or []
         # checksum buffers[0] must have after the warmup (None: only consistency is checked)
         self.expect_sum = None
+        # --dump-outputs: fn(last step index) -> [(name, buffer, row offsets, row bytes)], the bytes that step wrote
+        self.outputs = None
+
+
+DUMP_BUDGET = 48 << 20  # bytes of .npy payload per run (float32: a quarter as many output bytes)
+DUMP_SLICE = 4096       # bytes per sampled slice of an output row
+DUMP_SEED = 0xD0C5
+
+
+def _rows(base, count, pitch):
+    """Byte offsets of `count` rows `pitch` apart from `base`."""
+    import numpy as np
+
+    return base + np.arange(count, dtype=np.int64) * pitch
+
+
+def _chunk_rows(chunks, cst, stripe, ns):
+    """Byte offsets of the given chunks of every stripe of a [stripe][chunk][byte] batch."""
+    import numpy as np
+
+    return (np.arange(ns, dtype=np.int64)[:, None] * stripe + np.asarray(list(chunks), dtype=np.int64)[None, :] * cst).ravel()
+
+
+def dump_outputs(wl, last_step, directory, rank, world):
+    """Write what the last timed step wrote to device memory as
+    directory/<name>.npy (float32, one value per byte).  An output within its
+    share of DUMP_BUDGET is written whole, row after row; of a larger one a
+    fixed sample: DUMP_SLICE-byte slices at offsets drawn from a generator
+    seeded with DUMP_SEED (the first and last slice of the first and last row
+    always among them), so two runs with the same arguments sample the same
+    bytes.  Ranks past 0 write <name>_rank<r>.npy."""
+    import numpy as np
+
+    outs = wl.outputs(last_step)
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET // 4 // max(1, world) // max(1, len(outs))  # output bytes per array
+    rng = np.random.default_rng(DUMP_SEED)
+    written = {}
+    for name, buf, offs, rowlen in outs:
+        offs = np.asarray(offs, dtype=np.int64)
+        assert len(offs) and int(offs.min()) >= 0 and int(offs.max()) + rowlen <= buf.nbytes, name
+        if len(offs) * rowlen <= share:
+            parts = [buf.download(rowlen, int(o)) for o in offs]
+        else:
+            sl = min(DUMP_SLICE, rowlen)
+            nsl = max(4, share // sl)
+            rows = rng.integers(0, len(offs), size=nsl)
+            starts = rng.integers(0, (rowlen - sl) // 16 + 1, size=nsl) * 16 if rowlen > sl else np.zeros(nsl, np.int64)
+            rows[:4] = (0, 0, len(offs) - 1, len(offs) - 1)
+            starts[:4] = (0, rowlen - sl, 0, rowlen - sl)
+            parts = [buf.download(sl, int(offs[r]) + int(s)) for r, s in zip(rows, starts)]
+        arr = np.concatenate(parts).astype(np.float32)
+        fname = name if rank == 0 else f"{name}_rank{rank}"
+        np.save(os.path.join(directory, fname + ".npy"), arr)
+        written[fname] = int(arr.size)
+    return written
 
 
 def erase_checks(wl, ctx, want):
@@ -353,8 +425,11 @@ def wl_rs10_4(args, ctx, stream, rank):
     # encode and the 4-row recovers are launches of the same kernel
     # (k_mul_vec<10, 8, ...>): the roofline averages all of them, as rocprofv3's
     # per-kernel mean does
-    return Workload("rs10_4", "GiB/s RS(10,4) encode+decode, 1 MiB chunks, device-resident", config, ops, [buf],
-                    f"{kern} K={k} rows={p} work-queue (encode + recover launches)", ns, roof_ops=2, erase=erase)
+    wl = Workload("rs10_4", "GiB/s RS(10,4) encode+decode, 1 MiB chunks, device-resident", config, ops, [buf],
+                  f"{kern} K={k} rows={p} work-queue (encode + recover launches)", ns, roof_ops=2, erase=erase)
+    wl.outputs = lambda i: [("parity", buf, _chunk_rows(range(k, n), cst, stripe, ns), cs),
+                            ("recovered", buf, _chunk_rows(PATTERNS[i % len(PATTERNS)], cst, stripe, ns), cs)]
+    return wl
 
 
 def wl_decode_full(args, ctx, stream, rank):
@@ -377,9 +452,11 @@ def wl_decode_full(args, ctx, stream, rank):
 
     # parity-only loss: every output row is a pass-through of its data chunk,
     # so the output is the data itself -- the checksum every pattern must give
-    dec(PATTERNS[1])
-    ctx.sync()
-    copy_sum = out.checksum()
+    copy_sum = None
+    if args.full:
+        dec(PATTERNS[1])
+        ctx.sync()
+        copy_sum = out.checksum()
     ops = [("decode_full", lambda i: dec(PATTERNS[i % len(PATTERNS)]), ns * 2 * k * cs)]
     config = {
         "workload": f"RS(10,4) (n,k)=({n},{k}) full-output decode (all k data chunks, rs.cc:114,228-230), "
@@ -394,6 +471,7 @@ def wl_decode_full(args, ctx, stream, rank):
                   "device-resident", config, ops, [out, buf], f"{kern} K={k} copy-through (full-output decode)", ns,
                   erase=erase)
     wl.expect_sum = copy_sum
+    wl.outputs = lambda i: [("decoded", out, _rows(0, ns * k, cs), cs)]
     return wl
 
 
@@ -427,8 +505,11 @@ def wl_repair12(args, ctx, stream, rank):
     kern = config["launch"]["kernel"]
     zero = lambda: _zero_chunks(buf, [failed], cst, stripe, cs, ns, stream)  # noqa: E731
     erase = [("repair_fused", zero, lambda: ops[0][1](0)), ("repair_car_unfused", zero, lambda: unfused(0))]
-    return Workload("repair12", "GiB/s RS(12,4) single-failure repair, 1 MiB chunks, device-resident", config, ops,
-                    [buf, part], f"{kern} K={k} rows=1 (fused recover)", ns, erase=erase)
+    wl = Workload("repair12", "GiB/s RS(12,4) single-failure repair, 1 MiB chunks, device-resident", config, ops,
+                  [buf, part], f"{kern} K={k} rows=1 (fused recover)", ns, erase=erase)
+    wl.outputs = lambda i: [("repaired", buf, _chunk_rows([failed], cst, stripe, ns), cs),
+                            ("car_partials", part, _rows(0, ns * G, cs), cs)]
+    return wl
 
 
 def wl_mixed16(args, ctx, stream, rank):
@@ -451,8 +532,11 @@ def wl_mixed16(args, ctx, stream, rank):
     zero = lambda cl: _zero_chunks(buf, cl, cst, stripe, cs, ns, stream)  # noqa: E731
     erase = [("encode", lambda: zero(range(k, n)), lambda: ops[0][1](0))]
     erase += [(f"recover{pat}", lambda pat=pat: zero(pat), lambda i=i: ops[1][1](i)) for i, pat in enumerate(pats)]
-    return Workload("mixed16", f"GiB/s RS(16,4) encode+decode, {cs >> 10} KiB chunks, device-resident", config, ops,
-                    [buf], "k_mul_vec<K=16,R=8> (encode launch)", ns, erase=erase)
+    wl = Workload("mixed16", f"GiB/s RS(16,4) encode+decode, {cs >> 10} KiB chunks, device-resident", config, ops,
+                  [buf], "k_mul_vec<K=16,R=8> (encode launch)", ns, erase=erase)
+    wl.outputs = lambda i: [("parity", buf, _chunk_rows(range(k, n), cst, stripe, ns), cs),
+                            ("recovered", buf, _chunk_rows(pats[i % 3], cst, stripe, ns), cs)]
+    return wl
 
 
 def wl_write14(args, ctx, stream, rank):
@@ -476,8 +560,11 @@ def wl_write14(args, ctx, stream, rank):
                           f"{cs >> 10} KiB chunks, {ns} stripes per GPU", "stripes_per_gpu": ns, "chunk_bytes": cs,
               "byte_accounting": "n*cs per stripe: one HBM pass (k*cs read, (n-k)*cs written); the MD5 of all n "
                                  "chunks reads the same bytes from LDS"}
-    return Workload("write14", "GiB/s RS(10,4) encode + per-chunk MD5, 1 MiB chunks, device-resident", config, ops,
-                    [buf, dig], f"k_mul_md5<K={k}> (fused encode + MD5; MD5-chain-bound, not HBM-bound)", ns)
+    wl = Workload("write14", "GiB/s RS(10,4) encode + per-chunk MD5, 1 MiB chunks, device-resident", config, ops,
+                  [buf, dig], f"k_mul_md5<K={k}> (fused encode + MD5; MD5-chain-bound, not HBM-bound)", ns)
+    wl.outputs = lambda i: [("parity", buf, _chunk_rows(range(k, n), cs, stripe, ns), cs),
+                            ("md5", dig, _rows(0, 1, 0), dig.nbytes)]
+    return wl
 
 
 def wl_object(args, ctx, stream, rank):
@@ -517,8 +604,11 @@ def wl_object(args, ctx, stream, rank):
               "stripes_per_gpu": ns, "chunk_bytes": M,
               "byte_accounting": "write: n*cs per stripe (one fused encode + MD5 pass); read: full-output decode "
                                  "2k*cs per stripe"}
-    return Workload("object", "GiB/s object write (encode+MD5) + read (decode), RS(10,4), 1 MiB chunks, device-resident",
-                    config, ops, [obj, par, md5, chunks, out, cmd5, ok], "encode_object (fused k_mul_md5)", ns)
+    wl = Workload("object", "GiB/s object write (encode+MD5) + read (decode), RS(10,4), 1 MiB chunks, device-resident",
+                  config, ops, [obj, par, md5, chunks, out, cmd5, ok], "encode_object (fused k_mul_md5)", ns)
+    wl.outputs = lambda i: [("parity", par, _rows(0, ns * p, M), M), ("md5", md5, _rows(0, 1, 0), md5.nbytes),
+                            ("object_read", out, _rows(0, ns * k, M), M), ("chunk_ok", ok, _rows(0, 1, 0), ok.nbytes)]
+    return wl
 
 
 # MD5 chain of one 256-byte step of one chunk (4 blocks), measured alone with
@@ -605,12 +695,20 @@ def wl_files(args, ctx, stream, rank):
                                   "note": "one lane's MD5 chain per chunk, a slot's requests back to back: the "
                                           "longest slot's 256-byte steps x the bare chain's step time "
                                           "(profiles/r02_encode_md5_role_probes.log)"}}
-    return Workload("files", "GiB/s multi-file write (encode+MD5), RS(10,4), 1 MiB max chunk, device-resident",
-                    config, ops, [arena, par, tail, md5],
-                    "k_files_md5<10> (encode_objects_ex(TAIL_INPLACE | ASYNC): one launch codes and hashes every "
-                    "stripe, last stripes read in place with their partial chunk masked and stored to the tail arena)",
-                    total, roof_bytes=kernel_bytes,
-                    kernel_timer=(lambda: ctx.kernel_timing(True), ctx.kernel_time))
+    wl = Workload("files", "GiB/s multi-file write (encode+MD5), RS(10,4), 1 MiB max chunk, device-resident",
+                  config, ops, [arena, par, tail, md5],
+                  "k_files_md5<10> (encode_objects_ex(TAIL_INPLACE | ASYNC): one launch codes and hashes every "
+                  "stripe, last stripes read in place with their partial chunk masked and stored to the tail arena)",
+                  total, roof_bytes=kernel_bytes,
+                  kernel_timer=(lambda: ctx.kernel_timing(True), ctx.kernel_time))
+    if args.dump_outputs:
+        # the call leaves the parity slots past a short last stripe and the unused tail slots alone: the dump
+        # must not carry what the allocation held before
+        for b in (par, tail, md5):
+            b.memset(0)
+    wl.outputs = lambda i: [("parity", par, _rows(0, total * p, M), M), ("tail", tail, _rows(0, 1, 0), tail.nbytes),
+                            ("md5", md5, _rows(0, 1, 0), md5.nbytes)]
+    return wl
 
 
 CONFIG1 = ((6, 4, 1 << 20, "RS(4,2) read as (n,k)=(6,4), 4 MiB file, 1 MiB chunks"),
@@ -639,8 +737,12 @@ def wl_config1(args, ctx, stream, rank):
                           "chunks; encode + (n-k)-erasure recover per geometry",
               "geometries": [g[3] for g in CONFIG1],
               "byte_accounting": "encode n*cs + recover (k+e)*cs per stripe"}
-    return Workload("config1", "GiB/s RS(4,2) 4 MiB-file encode+decode (config 1), device-resident", config, ops,
-                    bufs, "k_mul_vec (single-stripe encode launch, latency bound)", 1)
+    wl = Workload("config1", "GiB/s RS(4,2) 4 MiB-file encode+decode (config 1), device-resident", config, ops,
+                  bufs, "k_mul_vec (single-stripe encode launch, latency bound)", 1)
+    wl.outputs = lambda i: [(f"{what}_{n}_{k}", b, _chunk_rows(ch, cs, n * cs, 1), cs)
+                            for b, (n, k, cs, _) in zip(bufs, CONFIG1)
+                            for what, ch in (("parity", range(k, n)), ("recovered", range(n - k)))]
+    return wl
 
 
 def cpu_baseline_config1(args):
@@ -896,7 +998,7 @@ def main():
     nxec.device_sync()
     # every op is idempotent on a consistent batch (re-encode / recover rewrite
     # the same bytes), so the batch checksum must not change across the timed steps
-    sum_before = wl.buffers[0].checksum()
+    sum_before = wl.buffers[0].checksum() if args.full else None
 
     evs = [[nxec.Event() for _ in range(nops + 1)] for _ in range(args.steps)]
     grp.barrier()
@@ -917,16 +1019,22 @@ def main():
     window = grp.max(t1) + grp.max(-t0)
     total_bytes = grp.sum(float(step_bytes * args.steps))
     numa_nodes = [int(v) for v in grp.gather(numa_node)]
-    consistent = wl.buffers[0].checksum() == sum_before and wl.expect_sum in (None, sum_before)
-    verified = grp.sum(0.0 if consistent else 1.0) == 0.0
-    # outside the timed region: erase chunks for real and rebuild them
-    rebuilt = erase_checks(wl, ctx, sum_before)
-    verified = grp.sum(0.0 if verified and all(rebuilt.values()) else 1.0) == 0.0
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step left in device memory, before anything below touches the batch
+        dumped = dump_outputs(wl, args.steps - 1, args.dump_outputs, rank, world)
+    verified, rebuilt = None, {}
+    if args.full:
+        consistent = wl.buffers[0].checksum() == sum_before and wl.expect_sum in (None, sum_before)
+        verified = grp.sum(0.0 if consistent else 1.0) == 0.0
+        # outside the timed region: erase chunks for real and rebuild them
+        rebuilt = erase_checks(wl, ctx, sum_before)
+        verified = grp.sum(0.0 if verified and all(rebuilt.values()) else 1.0) == 0.0
 
     # on-box copy ceiling: hipMemcpyDtoD of 16 GiB inside the
     # workload buffer, after the checksum above (it overwrites data)
     ceiling = None
-    if rank == 0 and wl.buffers[0].nbytes >= (32 << 30):
+    if args.full and rank == 0 and wl.buffers[0].nbytes >= (32 << 30):
         half = 16 << 30
         e0, e1 = nxec.Event(), nxec.Event()
         wl.buffers[0].copy_within(half, 0, half, stream)  # warm
@@ -969,8 +1077,10 @@ def main():
             "vs_baseline": None,
             "dtype": "u8",
             "data": "synthetic (splitmix64 bytes, device-generated)",
+            "full": args.full,
             "verified": verified,
             "verified_rebuilds": rebuilt or None,
+            "outputs": dumped,
             "config": dict(wl.config, parallelism=f"stripe-sharded x{world}, no collectives"),
             "numa_node_per_rank": numa_nodes,
             "ranks_window": None if world == 1 else {
@@ -1007,27 +1117,30 @@ def main():
             k, cs = args.k, args.chunk
             result["user_data_gib_s"] = round(2 * wl.stripes * k * cs * args.steps * world / elapsed / GIB, 2)
     headline_n1 = rank == 0 and world == 1 and wl.name == "rs10_4"
-    if args.host_inclusive and world > 1 and wl.name == "rs10_4":
+    # legs with runs of their own: only with --full
+    host_incl = args.full and args.host_inclusive
+    cpu_base = args.full and not args.no_cpu_baseline
+    if host_incl and world > 1 and wl.name == "rs10_4":
         # every rank at once: the host-resident encode over each GPU's own link
         hi = host_inclusive_ranks(ctx, grp, args.n, args.k, args.chunk)
         if rank == 0:
             result["host_inclusive"] = hi
-    if args.host_inclusive and headline_n1:
+    if host_incl and headline_n1:
         result["host_inclusive"] = host_inclusive(ctx, args.n, args.k, args.chunk)
-    if args.host_inclusive and wl.name == "rs10_4":
+    if host_incl and wl.name == "rs10_4":
         # the unmodified drop-in over every visible GPU (one process, the
         # default pool), rank 0 only while the other ranks wait
         grp.barrier()
         if rank == 0:
             result.setdefault("host_inclusive", {})["dropin_pool"] = dropin_pool_rate(orig_affinity)
         grp.barrier()
-    if (headline_n1 or (rank == 0 and world == 1 and wl.name == "config1")) and not args.no_cpu_baseline:
+    if (headline_n1 or (rank == 0 and world == 1 and wl.name == "config1")) and cpu_base:
         os.sched_setaffinity(0, orig_affinity)  # the host's CPUs, not only the GPU's node
-    if headline_n1 and not args.no_cpu_baseline:
+    if headline_n1 and cpu_base:
         result["cpu_baseline"] = cpu_baseline(args, args.n, args.k, args.chunk)
-        if args.host_inclusive:
+        if host_incl:
             result["cpu_baseline"]["write_path_with_md5"] = cpu_write_path(args, args.n, args.k, args.chunk)
-    if rank == 0 and world == 1 and wl.name == "config1" and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and wl.name == "config1" and cpu_base:
         by = cpu_baseline_config1(args)
         first = by[CONFIG1[0][3]]
         ref_v = first.get("GiB_s_reference_base_c_1t")

@@ -86,6 +86,64 @@ def test_pmc_summaries_are_labelled_passes():
                                          for d in doc["dispatches"]), name
 
 
+class FakeDev:
+    """Stand-in for nxec.DeviceBuffer: host bytes behind download()."""
+
+    def __init__(self, arr):
+        self.arr, self.nbytes = arr, arr.nbytes
+
+    def download(self, nbytes, offset=0):
+        assert 0 <= offset and offset + nbytes <= self.nbytes
+        return self.arr[offset:offset + nbytes].copy()
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: a small output is written whole, a large one as a fixed
+    seeded sample within the budget (first and last slice of the first and
+    last row included); two dumps of the same bytes are identical, a changed
+    sampled byte shows."""
+    import numpy as np
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4 * 2 * 64 * 1024)  # 64 KiB of output bytes per array
+    rowlen, pitch, nrows = 8192, 10000, 64
+    big = np.random.default_rng(5).integers(0, 256, size=nrows * pitch, dtype=np.uint8)
+    small = np.arange(48, dtype=np.uint8)
+    wl = bench.Workload("t", "m", {}, [], [], "k", 1)
+    wl.outputs = lambda i: [("big", FakeDev(big), bench._rows(0, nrows, pitch), rowlen),
+                            ("small", FakeDev(small), bench._rows(0, 3, 16), 16)]
+    a, b = tmp_path / "a", tmp_path / "b"
+    wrote = bench.dump_outputs(wl, 0, str(a), 0, 1)
+    bench.dump_outputs(wl, 0, str(b), 0, 1)
+    assert sorted(os.listdir(a)) == ["big.npy", "small.npy"]
+    got = {n: np.load(a / f"{n}.npy") for n in ("big", "small")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert wrote == {"big": got["big"].size, "small": 48}
+    assert np.array_equal(got["small"], small.astype(np.float32))
+    sl = bench.DUMP_SLICE
+    assert got["big"].size == 64 * 1024 and got["big"].nbytes + got["small"].nbytes <= bench.DUMP_BUDGET
+    assert np.array_equal(got["big"][:sl], big[:sl])
+    assert np.array_equal(got["big"][sl:2 * sl], big[rowlen - sl:rowlen])
+    last = (nrows - 1) * pitch
+    assert np.array_equal(got["big"][3 * sl:4 * sl], big[last + rowlen - sl:last + rowlen])
+    for n in got:
+        assert np.array_equal(got[n], np.load(b / f"{n}.npy"))
+    big[last + rowlen - 1] ^= 1
+    bench.dump_outputs(wl, 0, str(b), 0, 1)
+    assert not np.array_equal(got["big"], np.load(b / "big.npy"))
+    # ranks past 0 write their own files
+    bench.dump_outputs(wl, 0, str(b), 1, 2)
+    assert os.path.exists(b / "big_rank1.npy")
+
+
+def test_plain_run_options():
+    """--full is off by default and --steps is the number of timed steps the
+    line's ms_per_step divides by."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 3)
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
 def test_lib_hash_is_sixteen_hex_digits():
     h = bench.lib_sha16()
     assert len(h) == 16 and int(h, 16) >= 0

@@ -24,7 +24,7 @@ if has smoke; then
   tail -1 $OUT/smoke.log
 fi
 if has bench; then
-  timeout -k 10 500 python bench.py ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; stop bench $?; }
+  timeout -k 10 500 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; stop bench $?; }
   python3 -c "import json; d=json.load(open('$OUT/bench.json')); print('headline', d['value'], d['roofline']['frac'], d['verified'])"
 fi
 if has cfg; then
@@ -32,7 +32,7 @@ if has cfg; then
   IFS=';' read -ra CFGS <<< "$CFG_LIST"
   for c in "${CFGS[@]}"; do
     w=${c%%:*}; extra=""; [ "$c" != "$w" ] && extra=${c#*:}
-    timeout -k 10 300 python bench.py --workload $w $extra --steps ${CFG_STEPS:-20} --no-cpu-baseline --no-host-inclusive \
+    timeout -k 10 300 python bench.py --full --workload $w $extra --steps ${CFG_STEPS:-20} --no-cpu-baseline --no-host-inclusive \
       >> $OUT/configs.jsonl 2>> $OUT/configs.err || { tail -20 $OUT/configs.err; stop "cfg $c" $?; }
     tail -1 $OUT/configs.jsonl | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['metric'][:60], d['value'], d['roofline']['frac'], d['ms_per_step'], d['verified'])"
   done

@@ -24,7 +24,7 @@ if has tests; then
   tail -1 $OUT/smoke.log
 fi
 if has bench; then
-  timeout -k 10 500 python bench.py > $OUT/bench_final.json 2> $OUT/bench_final.err || stop bench $?
+  timeout -k 10 500 python bench.py --full > $OUT/bench_final.json 2> $OUT/bench_final.err || stop bench $?
   python3 -c "import json; d=json.load(open('$OUT/bench_final.json')); print('headline', d['value'], d['roofline']['frac'], d['verified'])"
 fi
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
@@ -60,14 +60,14 @@ if has cfg; then
               "mixed16|--chunk 262144 --layout tuned" "mixed16|--chunk 4194304 --layout tuned" \
               "mixed16|--chunk 65536 --layout tuned" "mixed16|--chunk 1048576 --layout tuned"; do
     IFS='|' read -r w extra <<< "$spec"
-    timeout -k 10 300 python bench.py --workload $w $extra --steps 10 --warmup 2 --no-cpu-baseline --no-host-inclusive \
+    timeout -k 10 300 python bench.py --full --workload $w $extra --steps 10 --warmup 2 --no-cpu-baseline --no-host-inclusive \
       > $OUT/cfg.json 2> $OUT/cfg.err || stop cfg_$w $?
     cat $OUT/cfg.json >> $OUT/configs_final.jsonl
     python3 -c "import json; d=json.load(open('$OUT/cfg.json')); print('$w $extra', d['ms_per_step'], d['roofline']['frac'], d['verified'])"
   done
 fi
 if has group; then
-  timeout -k 10 300 python bench.py --gpus 8 --group --stripes 512 --steps 10 --warmup 2 --no-cpu-baseline \
+  timeout -k 10 300 python bench.py --full --gpus 8 --group --stripes 512 --steps 10 --warmup 2 --no-cpu-baseline \
     --no-host-inclusive > $OUT/group8.json 2> $OUT/group8.err || stop group $?
   python3 -c "import json; d=json.load(open('$OUT/group8.json')); print('group8', d['value'], d['verified'], d['group']['value'], d['group']['verified'])"
 fi
