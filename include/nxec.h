@@ -225,6 +225,55 @@ int nxec_rs_recover_stripes(nxec_ctx_t *ctx, int n, int k, const int32_t *failed
                             unsigned char *d_stripes, int64_t chunk_stride, int64_t stripe_stride, int64_t len,
                             int64_t nstripes, void *stream);
 
+/* Parity scrub: are the n chunks of every stripe still a codeword, and if
+ * not, which chunk is wrong?  Needs no stored digests, and sees a torn stripe
+ * (data rewritten, parity not) that nxec_md5_verify_chunks cannot.
+ *
+ * The syndrome of byte i of stripe s is
+ *   sigma_r = p_r[i] ^ XOR_{j<k} c(r,j) (x) d_j[i],   r < n-k,
+ * with c the parity rows of nxec_gf_gen_rs_matrix(n, k).  d_status[s] (DEVICE
+ * array of nstripes int32) receives
+ *   NXEC_SCRUB_CLEAN      every syndrome byte of the stripe is zero;
+ *   a chunk id 0..n-1     (NXEC_SCRUB_LOCATE) every byte with a non-zero
+ *                         syndrome is explained by that one chunk: a data chunk
+ *                         j when sigma_r = c(r,j) (x) e for one e, a parity chunk
+ *                         r' when only sigma_r' is non-zero;
+ *   NXEC_SCRUB_UNLOCATED  the stripe is inconsistent and no single chunk
+ *                         explains it, or n-k == 1, or LOCATE was not asked.
+ * *d_nbad (optional DEVICE counter, not reset by the call) grows by the number
+ * of stripes that are not clean.  With NXEC_SCRUB_REPAIR (implies LOCATE) a
+ * located stripe is healed in place -- d_c[i] ^= e, or p_r'[i] ^= sigma_r' --
+ * only after the whole stripe agreed on one chunk; the status keeps the id
+ * that was healed.  Without REPAIR nothing is written into d_stripes, and a
+ * clean batch causes no stores at all beyond the statuses' reset.
+ *
+ * What the code's distance allows: a single corrupt chunk is always located
+ * when n-k >= 2 (any two columns of [C | I] are independent).  With n-k == 2
+ * two corrupt chunks at the same byte offsets can look like a third one, so a
+ * caller that cannot rule that out should not pass REPAIR; with n-k >= 3 (any
+ * three columns independent) that case reports UNLOCATED.  Corruption of two
+ * chunks at different offsets reports UNLOCATED for every n-k >= 2.
+ *
+ * Asynchronous on `stream`, no host synchronisation inside (the locate / heal
+ * stage decides on the device which stripes to visit).  Arguments as
+ * nxec_rs_encode_stripes; flags outside LOCATE|REPAIR or a NULL d_status give
+ * NXEC_ERR_INVALID before any device use.  len == 0 or nstripes == 0 launches
+ * nothing (n == k: nothing to check); the statuses are then set to CLEAN. */
+#define NXEC_SCRUB_CLEAN (-1)
+#define NXEC_SCRUB_UNLOCATED (-2)
+#define NXEC_SCRUB_LOCATE 1
+#define NXEC_SCRUB_REPAIR 2 /* implies LOCATE */
+int nxec_rs_scrub_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripes, int64_t chunk_stride,
+                          int64_t stripe_stride, int64_t len, int64_t nstripes, int flags, int32_t *d_status,
+                          unsigned long long *d_nbad, void *stream);
+
+/* The per-byte rule of the scrub on the host (no device): which single chunk
+ * explains the (n-k)-byte syndrome?  *chunk = NXEC_SCRUB_CLEAN (all zero), a
+ * chunk id with *error = the value to XOR into that chunk's byte, or
+ * NXEC_SCRUB_UNLOCATED (always, for a non-zero syndrome with n-k == 1).
+ * `error` may be NULL. */
+int nxec_rs_syndrome_locate(int n, int k, const unsigned char *syndrome, int32_t *chunk, unsigned char *error);
+
 /* Full-output decode with RSCode::decode semantics (rs.cc:111-236, non-repair):
  * inputs = the first k alive chunks of d_stripes (ascending ids; `failed`
  * lists the erased ids), output = all k data chunks into d_out

@@ -60,6 +60,8 @@ _PROTOS = {
     "nxec_stripes_mul_ptrs": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, i64, i64, vp]),
     "nxec_rs_encode_stripes": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, i64, i64, i64, vp]),
     "nxec_rs_recover_stripes": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, i64, i64, i64, i64, vp]),
+    "nxec_rs_scrub_stripes": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, i64, i64, i64, C.c_int, vp, vp, vp]),
+    "nxec_rs_syndrome_locate": (C.c_int, [C.c_int, C.c_int, vp, i32p, u8p]),
     "nxec_rs_decode_stripes": (
         C.c_int,
         [vp, C.c_int, C.c_int, vp, C.c_int, vp, i64, i64, vp, i64, i64, i64, i64, vp],
@@ -191,6 +193,11 @@ NXEC_ERR_INVALID = -2
 NXEC_ERR_HIP = -3
 NXEC_ERR_NOMEM = -4
 NXEC_ERR_NODEV = -5
+
+NXEC_SCRUB_CLEAN = -1
+NXEC_SCRUB_UNLOCATED = -2
+NXEC_SCRUB_LOCATE = 1
+NXEC_SCRUB_REPAIR = 2
 
 
 class NxecError(RuntimeError):

@@ -118,6 +118,39 @@ struct Md5Region {
 int launch_md5(const Md5Region *regions, int nregions, void *stream, unsigned long long *nbad = nullptr);
 int launch_checksum(const void *d, size_t bytes, uint64_t *d_out, void *stream);
 
+// Parity scrub (nxec_rs_scrub_stripes), detect stage: one pass checks
+// m.rows (<= 4) parity rows of every stripe against the k data chunks
+// (m.src_off[j], j < k; m.coef rows x k) and clears bit 0 of status[s]
+// (CLEAN -> UNLOCATED) of every stripe with a non-zero syndrome byte.  Reads
+// only; m.dst is unused.  The vector kernels take the pass's parity chunks as
+// sources k .. k+rows-1 of the tile loader (m.src_off[k + r] = par_off[r]),
+// so they exist for k + rows <= kScrubMaxSrc, k <= kScrubMaxK and
+// scrub_vec_rows(rows); every other shape, a layout that is not 16-byte
+// aligned and the sub-16-byte tail of a chunk go through the byte kernel.
+constexpr int kScrubMaxSrc = 20;
+constexpr int kScrubMaxK = 16;
+struct ScrubArgs {
+  MulArgs m;
+  int32_t *status;
+  uint32_t par_off[kMaxRowsPerPass];
+};
+bool scrub_vec_shape(int k, int rows);
+int launch_scrub_detect(const ScrubArgs &a, bool vec_ok, int num_cus, void *stream);
+// Locate / heal stage: workgroup s leaves at once unless status[s] != CLEAN;
+// counts the stripe into *nbad (optional); with NXEC_SCRUB_LOCATE recomputes
+// its syndromes (coef: DEVICE (n-k) x k parity rows), reduces the per-byte
+// explaining chunk (nxec_scrub_rule.h) over the stripe into status[s], and
+// with NXEC_SCRUB_REPAIR applies the correction in a second sweep.
+struct ScrubLocateArgs {
+  uint8_t *base;
+  int64_t chunk_stride, stripe_stride, len, nstripes;
+  int32_t n, k, flags;
+  int32_t *status;
+  unsigned long long *nbad;
+  const uint8_t *coef;
+};
+int launch_scrub_locate(const ScrubLocateArgs &a, void *stream);
+
 // Variable-length batch (many objects per call): stripe s has its own chunk
 // length and layout.  Source chunk j at src + j*src_cs, output row r at
 // dst + r*dst_cs.  prefix[s] = first 16-byte unit of stripe s (prefix[n] = total).

@@ -37,6 +37,7 @@
 
 #include "nxec_device.h"
 #include "nxec_internal.h"
+#include "nxec_scrub_rule.h"
 
 namespace nxec {
 
@@ -164,6 +165,47 @@ struct LdsBody {
     for (int j = 0; j < K; j++) lookup16<R>(tlane + j * 1024 * R, d[j], acc);
     store_rows<GATHER>(a, s, vg, acc);
     copy_through<K, COPY>(a, s, vg, d);
+  }
+};
+
+// --- parity scrub, detect stage (nxec_rs_scrub_stripes): LdsBody without stores ---
+// The pass's ROWS parity chunks are sources KD .. KD+ROWS-1 of the tile loader
+// (so tile_loop's vmcnt accounting sees every load of the step); only the KD
+// data sources are looked up.  The recomputed rows are XORed with the loaded
+// parity vectors and ORed into one per-lane register; a wave that saw a
+// non-zero syndrome clears bit 0 of its stripe's status (CLEAN -> UNLOCATED)
+// with one atomic.  A clean tile stores nothing.
+__device__ __forceinline__ void scrub_flag(int32_t *status, uint32_t s) {
+  __hip_atomic_fetch_and(status + s, ~1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <int KD, int ROWS, int R>
+struct ScrubBody {
+  static constexpr int K = KD + ROWS;
+  static constexpr int kLds = KD * 1024 * R;
+  static __device__ __forceinline__ void setup(const MulArgs &a, uint32_t *tab) {
+    build_tables<R>(a.coef, KD, ROWS, tab);
+  }
+  const char *tlane;
+  int32_t *status;
+  __device__ ScrubBody(const uint32_t *tab, int32_t *st)
+      : tlane(reinterpret_cast<const char *>(tab) + (threadIdx.x % R) * 4), status(st) {}
+  __device__ __forceinline__ void operator()(const MulArgs &, uint32_t s, uint32_t, const u32x4 (&d)[K]) const {
+    uint32_t acc[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) acc[i] = 0;
+#pragma unroll
+    for (int j = 0; j < KD; j++) lookup16<R>(tlane + j * 1024 * R, d[j], acc);
+    uint32_t o[4][4];
+    rows_of(acc, o);
+    uint32_t bad = 0;
+#pragma unroll
+    for (int r = 0; r < ROWS; r++)
+      bad |= (o[r][0] ^ d[KD + r].x) | (o[r][1] ^ d[KD + r].y) | (o[r][2] ^ d[KD + r].z) | (o[r][3] ^ d[KD + r].w);
+    const uint64_t hit = __ballot(bad != 0);
+    if (hit != 0) {  // wave-uniform, taken only on corruption
+      if (static_cast<int>(__lane_id()) == __ffsll(static_cast<unsigned long long>(hit)) - 1) scrub_flag(status, s);
+    }
   }
 };
 
@@ -550,6 +592,106 @@ __global__ __launch_bounds__(256) void k_mul_bytes(const MulArgs a) {
   }
 }
 
+// --- parity scrub kernels (nxec_rs_scrub_stripes) ---
+// Detect, vector form: K = KD + ROWS sources per lane through the work-queue
+// tile loop (prefetch while 2 x 4K source registers fit the 128-VGPR budget).
+template <int KD, int ROWS, bool FULL>
+__global__ __launch_bounds__(kBlock) void k_scrub_vec(const ScrubArgs a) {
+  constexpr int K = KD + ROWS;
+  constexpr int R = KD <= 9 ? 16 : 8;
+  constexpr bool PF = K <= (FULL ? kPrefetchMaxK : kPrefetchMaxKCopy);
+  using Body = ScrubBody<KD, ROWS, R>;
+  static_assert(K <= kScrubMaxSrc && queue_fits(Body::kLds), "scrub kernels are queue-driven");
+  extern __shared__ uint32_t tab[];
+  Body::setup(a.m, tab);
+  __syncthreads();
+  mul_tiles<K, false, FULL, PF, true>(a.m, Body(tab, a.status), tab + Body::kLds / 4);
+}
+
+// Detect, byte form: any k and alignment, chunk bytes [byte_begin, len).
+__global__ __launch_bounds__(256) void k_scrub_bytes(const ScrubArgs a) {
+  extern __shared__ uint32_t tab[];
+  const MulArgs &m = a.m;
+  const int k = m.k;
+  build_tables<1>(m, k, tab);
+  __syncthreads();
+  const int64_t span = m.len - m.byte_begin;
+  const int64_t total = span * m.nstripes;
+  for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < total;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const uint32_t s = static_cast<uint32_t>(i / span);
+    const int64_t pos = m.byte_begin + (i - static_cast<int64_t>(s) * span);
+    uint32_t acc = 0;
+    for (int j = 0; j < k; j++) acc ^= tab[j * 256 + src_chunk<false>(m, s, j)[pos]];
+    const uint8_t *stripe = m.src + static_cast<int64_t>(s) * m.src_stripe_stride;
+    uint32_t par = 0;
+    for (int r = 0; r < m.rows; r++) par |= static_cast<uint32_t>(stripe[a.par_off[r] + pos]) << (8 * r);
+    if (acc != par) scrub_flag(a.status, s);
+  }
+}
+
+// Locate / heal: the rare path, one workgroup per stripe, plain bytes.
+// Dynamic LDS: the (n-k) x k coefficients, then 256 syndrome columns of n-k
+// bytes (syndrome r of thread t at [r*256 + t]).
+__global__ __launch_bounds__(256) void k_scrub_locate(const ScrubLocateArgs a) {
+  extern __shared__ uint32_t scrub_lds[];
+  __shared__ int s_lo, s_hi;
+  const int64_t s = blockIdx.x;
+  if (a.status[s] == scrub::kClean) return;  // uniform
+  const int tid = threadIdx.x;
+  if (tid == 0 && a.nbad) atomicAdd(a.nbad, 1ull);
+  const int n = a.n, k = a.k, m = n - k;
+  if (!(a.flags & NXEC_SCRUB_LOCATE) || m < 2) return;  // the detect stage left UNLOCATED
+  uint8_t *coef = reinterpret_cast<uint8_t *>(scrub_lds);
+  uint8_t *syn = coef + (m * k + 15) / 16 * 16 + tid;
+  for (int i = tid; i < m * k; i += 256) coef[i] = a.coef[i];
+  if (tid == 0) {
+    s_lo = INT32_MAX;
+    s_hi = INT32_MIN;
+  }
+  __syncthreads();
+  uint8_t *base = a.base + s * a.stripe_stride;
+  const int64_t cs = a.chunk_stride;
+  // sweep 1: the chunk that explains each inconsistent byte column
+  int32_t mine = scrub::kClean;
+  for (int64_t i = tid; i < a.len; i += 256) {
+    for (int r = 0; r < m; r++) syn[r * 256] = base[(k + r) * cs + i];
+    for (int j = 0; j < k; j++) {
+      const uint32_t x = base[j * cs + i];
+      for (int r = 0; r < m; r++) syn[r * 256] ^= static_cast<uint8_t>(gf_mul_dev(coef[r * k + j], x));
+    }
+    uint8_t e;
+    const int32_t c = scrub::locate(n, k, coef, [&](int r) { return syn[r * 256]; }, &e);
+    if (c != scrub::kClean) mine = (mine == scrub::kClean || mine == c) ? c : scrub::kUnlocated;
+  }
+  if (mine != scrub::kClean) {
+    atomicMin(&s_lo, mine);
+    atomicMax(&s_hi, mine);
+  }
+  __syncthreads();
+  const int32_t located = (s_lo == s_hi && s_lo >= 0) ? s_lo : scrub::kUnlocated;
+  if (tid == 0) a.status[s] = located;
+  if (!(a.flags & NXEC_SCRUB_REPAIR) || located < 0) return;
+  // sweep 2: the whole stripe agreed on one chunk; heal it
+  if (located >= k) {  // parity row r: p_r ^= sigma_r
+    const uint8_t *row = coef + (located - k) * k;
+    uint8_t *p = base + located * cs;
+    for (int64_t i = tid; i < a.len; i += 256) {
+      uint32_t v = 0;
+      for (int j = 0; j < k; j++) v ^= gf_mul_dev(row[j], base[j * cs + i]);
+      if (p[i] != static_cast<uint8_t>(v)) p[i] = static_cast<uint8_t>(v);
+    }
+  } else {  // data chunk c: e = sigma_0 / c(0, c)
+    const uint32_t ic = scrub::inv(coef[located]);
+    uint8_t *d = base + located * cs;
+    for (int64_t i = tid; i < a.len; i += 256) {
+      uint32_t s0 = base[k * cs + i];
+      for (int j = 0; j < k; j++) s0 ^= gf_mul_dev(coef[j], base[j * cs + i]);
+      if (s0) d[i] ^= static_cast<uint8_t>(gf_mul_dev(s0, ic));
+    }
+  }
+}
+
 // --- variable-length batches (many objects per call) ---
 // One launch over stripes of different chunk lengths and layouts.  Work unit =
 // one 16-byte column piece; workgroup b owns the contiguous unit run
@@ -769,6 +911,23 @@ constexpr std::array<KernelFn, sizeof...(Ks)> perm_table(std::integer_sequence<i
 const std::array<KernelFn, kPermMaxK> kPerm[2] = {perm_table<false>(std::make_integer_sequence<int, kPermMaxK>{}),
                                                   perm_table<true>(std::make_integer_sequence<int, kPermMaxK>{})};
 
+// scrub detect kernels: every k <= kScrubMaxK with 1..4 parity rows per pass
+// (k + rows <= kScrubMaxSrc), [rows-1][full][k-1]
+using ScrubFn = void (*)(ScrubArgs);
+using ScrubTable = std::array<ScrubFn, kScrubMaxK>;
+template <int ROWS, bool FULL, int... Ks>
+constexpr ScrubTable scrub_table(std::integer_sequence<int, Ks...>) {
+  return {{&k_scrub_vec<Ks + 1, ROWS, FULL>...}};
+}
+template <int ROWS>
+constexpr std::array<ScrubTable, 2> scrub_tables() {
+  return {{scrub_table<ROWS, false>(std::make_integer_sequence<int, kScrubMaxK>{}),
+           scrub_table<ROWS, true>(std::make_integer_sequence<int, kScrubMaxK>{})}};
+}
+const std::array<ScrubTable, 2> kScrub[kMaxRowsPerPass] = {scrub_tables<1>(), scrub_tables<2>(), scrub_tables<3>(),
+                                                           scrub_tables<4>()};
+int scrub_vec_lds(int k) { return k * 1024 * (k <= 9 ? 16 : 8) + kRingBytes; }
+
 int hip_fail(hipError_t e, const char *what) {
   return set_error(NXEC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
@@ -864,6 +1023,18 @@ int prepare_kernels() {
     hipError_t e = raise(fn, NXEC_MAX_K * 1024);
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(dyn/bytes)");
   }
+  for (int r = 0; r < kMaxRowsPerPass; r++)
+    for (int f = 0; f < 2; f++)
+      for (int k = 1; k <= kScrubMaxK; k++) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kScrub[r][f][k - 1]),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, scrub_vec_lds(k));
+        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_scrub_vec)");
+      }
+  {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_scrub_bytes),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, NXEC_MAX_K * 1024);
+    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_scrub_bytes)");
+  }
   return prepare_encode_md5();
 }
 
@@ -956,6 +1127,67 @@ int launch_mul(const MulArgs &a, bool vec_ok, int num_cus, void *stream) {
     if (e != hipSuccess) return hip_fail(e, "launch k_mul_bytes");
   }
   return NXEC_OK;
+}
+
+bool scrub_vec_shape(int k, int rows) {
+  return k >= 1 && k <= kScrubMaxK && rows >= 1 && rows <= kMaxRowsPerPass && k + rows <= kScrubMaxSrc;
+}
+
+int launch_scrub_detect(const ScrubArgs &a0, bool vec_ok, int num_cus, void *stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ScrubArgs a = a0;
+  MulArgs &m = a.m;
+  if (m.nstripes <= 0 || m.len <= 0 || m.rows <= 0) return NXEC_OK;
+  const bool vec = vec_ok && scrub_vec_shape(m.k, m.rows);
+  m.vec_begin = 0;
+  m.vec_count = vec ? m.len / 16 : 0;
+  m.byte_begin = m.vec_count * 16;
+  if (m.vec_count > 0) {
+    const int64_t tps = (m.vec_count + kBlock - 1) / kBlock;
+    if (tps * m.nstripes >= (int64_t(1) << 32) || m.vec_count >= (int64_t(1) << 32))
+      return set_error(NXEC_ERR_INVALID, "batch too large for one launch (split nstripes)");
+    for (int r = 0; r < m.rows; r++) m.src_off[m.k + r] = a.par_off[r];
+    // complete tiles first (no lane predicates), then the ragged remainder
+    const int64_t full = m.vec_count / kBlock * kBlock;
+    const int64_t parts[2][2] = {{0, full}, {full, m.vec_count - full}};
+    for (int pi = 0; pi < 2; pi++) {
+      if (parts[pi][1] <= 0) continue;
+      ScrubArgs b = a;
+      b.m.queue_slot = static_cast<int32_t>(g_next_slot.fetch_add(1, std::memory_order_relaxed) % kQueueSlots);
+      b.m.tiles_per_grab = tiles_per_grab(b.m);
+      // the encode's tile order (launch_mul): groups of 8 stripes for big chunks at an aliasing stride
+      const bool aliased = m.src_chunk_stride % (int64_t(1) << 20) == 0;
+      b.m.stripe_group = ((m.vec_count + kBlock - 1) / kBlock >= 128 && aliased) ? 8 : 1;
+      b.m.vec_begin = parts[pi][0];
+      b.m.vec_count = parts[pi][1];
+      const int64_t ntiles = (b.m.vec_count + kBlock - 1) / kBlock * b.m.nstripes;
+      const int64_t grid = std::min<int64_t>(num_cus, ntiles);
+      hipLaunchKernelGGL(kScrub[m.rows - 1][pi == 0][m.k - 1], dim3(static_cast<unsigned>(grid)), dim3(kBlock),
+                         scrub_vec_lds(m.k), st, b);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return launch_failed(e, "launch k_scrub_vec", b.m.queue_slot, st);
+    }
+  }
+  if (m.byte_begin < m.len) {
+    const int64_t total = (m.len - m.byte_begin) * m.nstripes;
+    int64_t blocks = (total + 255) / 256;
+    if (blocks > static_cast<int64_t>(num_cus) * 8) blocks = static_cast<int64_t>(num_cus) * 8;
+    hipLaunchKernelGGL(k_scrub_bytes, dim3(static_cast<unsigned>(blocks)), dim3(256), m.k * 1024, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "launch k_scrub_bytes");
+  }
+  return NXEC_OK;
+}
+
+int launch_scrub_locate(const ScrubLocateArgs &a, void *stream) {
+  if (a.nstripes <= 0) return NXEC_OK;
+  if (a.nstripes >= (int64_t(1) << 31)) return set_error(NXEC_ERR_INVALID, "scrub: too many stripes for one launch");
+  const int m = a.n - a.k;
+  const size_t lds = static_cast<size_t>((m * a.k + 15) / 16 * 16) + static_cast<size_t>(m) * 256;
+  hipLaunchKernelGGL(k_scrub_locate, dim3(static_cast<unsigned>(a.nstripes)), dim3(256), lds,
+                     static_cast<hipStream_t>(stream), a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? NXEC_OK : hip_fail(e, "launch k_scrub_locate");
 }
 
 int reset_work_queues(void *stream) {

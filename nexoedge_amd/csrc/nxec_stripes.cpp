@@ -118,6 +118,32 @@ int stripes_mul_impl(nxec_ctx_t *ctx, int rows, int k, const unsigned char *coef
   return NXEC_OK;
 }
 
+namespace {
+std::mutex g_scrub_coef_mu;
+std::map<std::tuple<int, int, int>, uint8_t *> g_scrub_coef;  // (device, n, k) -> device copy of the parity rows
+}  // namespace
+
+// The (n-k) x k parity rows of RS(n,k) in the device's memory, for the scrub's
+// locate stage: uploaded on the first call per (device, n, k) -- the only host
+// synchronisation of nxec_rs_scrub_stripes, once -- and kept for the process.
+static int scrub_coef(int device, int n, int k, const uint8_t *rows, const uint8_t **out) {
+  std::lock_guard<std::mutex> lk(g_scrub_coef_mu);
+  uint8_t *&d = g_scrub_coef[std::make_tuple(device, n, k)];
+  if (!d) {
+    const size_t bytes = static_cast<size_t>(n - k) * k;
+    uint8_t *p = nullptr;
+    NXEC_HIP(hipMalloc(reinterpret_cast<void **>(&p), bytes));
+    const hipError_t e = hipMemcpy(p, rows, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(p);
+      return hip_err(e, "scrub coefficient upload");
+    }
+    d = p;
+  }
+  *out = d;
+  return NXEC_OK;
+}
+
 }  // namespace nxec
 
 using namespace nxec;
@@ -180,6 +206,85 @@ int nxec_rs_recover_stripes(nxec_ctx_t *ctx, int n, int k, const int32_t *failed
   if (rc) return rc;
   return nxec_stripes_mul(ctx, nfailed, k, rm.data(), d_stripes, inputs.data(), chunk_stride, stripe_stride,
                           d_stripes, failed, chunk_stride, stripe_stride, nullptr, len, nstripes, stream);
+}
+
+int nxec_rs_scrub_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripes, int64_t chunk_stride,
+                          int64_t stripe_stride, int64_t len, int64_t nstripes, int flags, int32_t *d_status,
+                          unsigned long long *d_nbad, void *stream) {
+  if (!ctx) return set_error(NXEC_ERR_INVALID, "null context");
+  if (!valid_nk(n, k)) return set_error(NXEC_ERR_INVALID, "invalid (n,k)=(%d,%d)", n, k);
+  if (flags & ~(NXEC_SCRUB_LOCATE | NXEC_SCRUB_REPAIR)) return set_error(NXEC_ERR_INVALID, "scrub: unknown flags %d", flags);
+  if (len < 0 || nstripes < 0) return set_error(NXEC_ERR_INVALID, "negative len or nstripes");
+  if (!d_status) return set_error(NXEC_ERR_INVALID, "scrub: null status array");
+  if (flags & NXEC_SCRUB_REPAIR) flags |= NXEC_SCRUB_LOCATE;
+  const int m = n - k;
+  const bool work = len > 0 && nstripes > 0 && m > 0;
+  if (work && !d_stripes) return set_error(NXEC_ERR_INVALID, "null stripe buffer");
+  // chunk byte offsets inside a stripe stay 32-bit (the kernels' scalar address math)
+  if (work && (chunk_stride < 0 || static_cast<int64_t>(n - 1) * chunk_stride + len > (int64_t(1) << 32) - 1))
+    return set_error(NXEC_ERR_INVALID, "scrub: chunk offset out of range (chunks of a stripe must lie within 4 GiB)");
+  if (nstripes == 0) return NXEC_OK;
+  int rc = ensure_device(ctx->device);
+  if (rc) return rc;
+  hipStream_t st = pick_stream(ctx, stream);
+  NXEC_HIP(hipMemsetAsync(d_status, 0xFF, static_cast<size_t>(nstripes) * sizeof(int32_t), st));  // CLEAN
+  if (!work) return NXEC_OK;
+
+  std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
+  nxec_gf_gen_rs_matrix(enc.data(), n, k);  // rs.cc:26
+  const uint8_t *par = enc.data() + static_cast<size_t>(k) * k;
+
+  ScrubArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.m.src = d_stripes;
+  a.m.src_chunk_stride = chunk_stride;
+  a.m.src_stripe_stride = stripe_stride;
+  a.m.len = len;
+  a.m.k = k;
+  for (int j = 0; j < k; j++) {
+    a.m.src_off[j] = static_cast<uint32_t>(j * chunk_stride);
+    a.m.copy_off[j] = kNoCopy;
+  }
+  const bool vec_ok = aligned16(d_stripes) && chunk_stride % 16 == 0 && stripe_stride % 16 == 0;
+  // split nstripes so one launch's tile count fits 32 bits
+  const int64_t tps = std::max<int64_t>(1, (len / 16 + 1023) / 1024);
+  const int64_t max_stripes = std::max<int64_t>(1, ((int64_t(1) << 31) / tps));
+  // detect: one pass per 4 parity rows, every pass flagging the same status word
+  for (int r0 = 0; r0 < m; r0 += kMaxRowsPerPass) {
+    const int pr = std::min(kMaxRowsPerPass, m - r0);
+    a.m.rows = pr;
+    for (int r = 0; r < kMaxRowsPerPass; r++) {
+      a.par_off[r] = r < pr ? static_cast<uint32_t>((k + r0 + r) * chunk_stride) : 0;
+      for (int j = 0; j < k; j++) a.m.coef[r * k + j] = r < pr ? par[static_cast<size_t>(r0 + r) * k + j] : 0;
+    }
+    for (int64_t s0 = 0; s0 < nstripes; s0 += max_stripes) {
+      ScrubArgs b = a;
+      b.m.nstripes = std::min(max_stripes, nstripes - s0);
+      b.m.src = d_stripes + s0 * stripe_stride;
+      b.status = d_status + s0;
+      if ((rc = launch_scrub_detect(b, vec_ok, ctx->num_cus, st))) return rc;
+    }
+  }
+  if (!d_nbad && !(flags & NXEC_SCRUB_LOCATE)) return NXEC_OK;  // nothing left to count or locate
+  // locate / heal: the stage reads the parity rows from device memory, uploaded once per (device, n, k)
+  const uint8_t *d_coef = nullptr;
+  if ((rc = scrub_coef(ctx->device, n, k, par, &d_coef))) return rc;
+  for (int64_t s0 = 0; s0 < nstripes; s0 += (int64_t(1) << 30)) {
+    ScrubLocateArgs la{};
+    la.base = d_stripes + s0 * stripe_stride;
+    la.chunk_stride = chunk_stride;
+    la.stripe_stride = stripe_stride;
+    la.len = len;
+    la.nstripes = std::min(int64_t(1) << 30, nstripes - s0);
+    la.n = n;
+    la.k = k;
+    la.flags = flags;
+    la.status = d_status + s0;
+    la.nbad = d_nbad;
+    la.coef = d_coef;
+    if ((rc = launch_scrub_locate(la, st))) return rc;
+  }
+  return NXEC_OK;
 }
 
 int nxec_rs_decode_stripes(nxec_ctx_t *ctx, int n, int k, const int32_t *failed, int nfailed,

@@ -80,6 +80,24 @@ def decode_matrix(n: int, k: int, input_ids: Sequence[int], targets: Sequence[in
     return out[: len(targets)]
 
 
+SCRUB_CLEAN = _lib.NXEC_SCRUB_CLEAN
+SCRUB_UNLOCATED = _lib.NXEC_SCRUB_UNLOCATED
+SCRUB_LOCATE = _lib.NXEC_SCRUB_LOCATE
+SCRUB_REPAIR = _lib.NXEC_SCRUB_REPAIR
+
+
+def syndrome_locate(n: int, k: int, syndrome) -> tuple:
+    """nxec_rs_syndrome_locate: (chunk, error) -- the single chunk that explains an (n-k)-byte syndrome and the
+    value to XOR into its byte; chunk is SCRUB_CLEAN or SCRUB_UNLOCATED (error 0) otherwise."""
+    syn = np.ascontiguousarray(np.asarray(syndrome, dtype=np.uint8).reshape(-1))
+    if syn.size != n - k:
+        raise ValueError(f"syndrome has {syn.size} bytes, n-k = {n - k}")
+    chunk, err = C.c_int32(0), C.c_ubyte(0)
+    check(lib.nxec_rs_syndrome_locate(n, k, _u8(syn) if syn.size else None, C.byref(chunk), C.byref(err)),
+          "nxec_rs_syndrome_locate")
+    return chunk.value, err.value
+
+
 LAYOUT_RECOVER_HEAVY = 1
 OBJECTS_TAIL_INPLACE = 1  # nxec_encode_objects_ex: only the partial last-stripe chunk to the tail arena
 OBJECTS_ASYNC = 2  # nxec_encode_objects_ex: return once queued on the stream
@@ -469,6 +487,29 @@ class Context:
         check(lib.nxec_rs_recover_stripes(C.c_void_p(self.ptr), n, k, fp, len(failed), C.c_void_p(int(stripes)),
                                           chunk_stride, stripe_stride, length, nstripes, stream),
               "nxec_rs_recover_stripes")
+
+    def rs_scrub_stripes(self, n: int, k: int, stripes: int, chunk_stride: int, stripe_stride: int, length: int,
+                         nstripes: int, status: int, flags: int = 0, nbad=None, stream=None) -> None:
+        """nxec_rs_scrub_stripes (asynchronous): `status` is a device array of nstripes int32, `nbad` an
+        optional device uint64 counter the call adds to."""
+        check(lib.nxec_rs_scrub_stripes(C.c_void_p(self.ptr), n, k, C.c_void_p(int(stripes)), chunk_stride,
+                                        stripe_stride, length, nstripes, flags, C.c_void_p(int(status)),
+                                        C.c_void_p(int(nbad)) if nbad else None, stream), "nxec_rs_scrub_stripes")
+
+    def rs_scrub(self, n: int, k: int, stripes: int, chunk_stride: int, stripe_stride: int, length: int,
+                 nstripes: int, flags: int = 0, stream=None):
+        """Scrub a batch and wait: (int32 statuses [nstripes], number of stripes that are not clean)."""
+        cnt = (nstripes * 4 + 7) // 8 * 8
+        st = DeviceBuffer(cnt + 8)  # statuses, then the 8-byte aligned counter
+        stream = stream if stream is not None else self.stream  # the copies below in order with the scrub
+        try:
+            check(lib.nxec_memset(st.addr(cnt), 0, 8, stream), "memset")
+            self.rs_scrub_stripes(n, k, stripes, chunk_stride, stripe_stride, length, nstripes, st.ptr, flags,
+                                  st.ptr + cnt, stream)
+            raw = st.download(stream=stream)
+        finally:
+            st.free()
+        return raw[: nstripes * 4].view(np.int32).copy(), int(raw[cnt: cnt + 8].view(np.uint64)[0])
 
     def rs_decode(self, n: int, k: int, failed: Sequence[int], stripes: int, chunk_stride: int, stripe_stride: int,
                   out: int, out_chunk_stride: int, out_stripe_stride: int, length: int, nstripes: int,
