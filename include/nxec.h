@@ -785,6 +785,26 @@ int nxec_reset_work_queues(void);
 /* Testing only: store `next_tile` in the tile counter of the slot the next
  * coding launch will draw (simulates a launch that died mid-flight). */
 int nxec_debug_poison_next_queue_slot(uint32_t next_tile);
+/* Testing only: the launch record.  While enabled (process-wide; off by
+ * default, no environment setting turns it on) every coding-kernel launch
+ * appends one text line of space-separated key=value fields that names the
+ * kernel instantiation and its launch shape:
+ *   family=k_mul_vec k=10 rows=4 r=16 gather=0 copy=0 full=1 pf=1 q=1 tpg=1 sg=1 grid=256
+ * family is the kernel template (k_mul_vec, k_mul_perm, k_mul_vec_dyn,
+ * k_mul_bytes, k_scrub_vec (kd= data chunks, rows= parity rows), k_scrub_bytes,
+ * k_mul_ragged, k_mul_list, k_mul_md5, k_gather_md5, k_files_md5); r the LDS
+ * table replication; pf / q the instantiation's compile-time next-tile
+ * prefetch and work queue (q=1 with slot=-1: the static order was asked for);
+ * tpg tiles per queue grab; sg the stripe group of the tile order; the MD5
+ * families carry p= output rows, hsrc= / mask= / tstore= and spg= stripes
+ * (slots) per workgroup, and product=1 unless a design-probe variant took
+ * the launch.  Enabling or disabling clears the record.
+ * nxec_debug_launch_log_read returns the record's length in bytes; when it
+ * fits (length < len) it is copied to buf, NUL terminated, and cleared,
+ * otherwise nothing is copied or cleared (call again with a larger buffer).
+ * Lines past 4 MiB of unread record are dropped. */
+int nxec_debug_launch_log(int enable);
+int nxec_debug_launch_log_read(char *buf, int len);
 
 /* ---------------------------------------------------------------------------
  * 8. Storage-class / proxy INI files, for hosts that drive the coding path

@@ -148,6 +148,8 @@ _PROTOS = {
     "nxec_cxx_abi_self": (None, [vp]),
     "nxec_reset_work_queues": (C.c_int, []),
     "nxec_debug_poison_next_queue_slot": (C.c_int, [C.c_uint32]),
+    "nxec_debug_launch_log": (C.c_int, [C.c_int]),
+    "nxec_debug_launch_log_read": (C.c_int, [C.c_char_p, C.c_int]),
     "nxec_pci_numa_node": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "nxec_numa_node_cpus": (C.c_int, [C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
     "nxec_bind_thread_to_pci": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),

@@ -34,6 +34,28 @@ thread_local std::string g_last_error;
 const std::string &last_error() { return g_last_error; }
 void restore_error(const std::string &msg) { g_last_error = msg; }
 
+// The launch record (nxec_debug_launch_log): process-wide, one line per kernel launch while on.
+std::atomic<int> g_launch_log_on{0};
+namespace {
+std::mutex g_launch_log_mu;
+std::string g_launch_log;
+constexpr size_t kLaunchLogCap = size_t(4) << 20;
+}  // namespace
+
+void launch_log_append(const char *fmt, ...) {
+  char line[384];
+  va_list ap;
+  va_start(ap, fmt);
+  int n = std::vsnprintf(line, sizeof(line) - 1, fmt, ap);
+  va_end(ap);
+  if (n < 0) return;
+  n = std::min(n, static_cast<int>(sizeof(line)) - 2);
+  line[n++] = '\n';
+  std::lock_guard<std::mutex> lk(g_launch_log_mu);
+  if (!launch_log_on() || g_launch_log.size() + static_cast<size_t>(n) > kLaunchLogCap) return;
+  g_launch_log.append(line, static_cast<size_t>(n));
+}
+
 // Copy into pinned staging.  The NT-staging probe (nxec_tuning.h) uses
 // streaming (non-temporal) stores: the staging lines are never read by the
 // CPU, so skipping their read-for-ownership halves the DRAM traffic of a
@@ -1052,6 +1074,24 @@ int nxec_debug_poison_next_queue_slot(uint32_t next_tile) {
   NXEC_HIP(hipGetDevice(&dev));
   int rc = ensure_device(dev);
   return rc ? rc : debug_poison_next_queue_slot(next_tile);
+}
+
+int nxec_debug_launch_log(int enable) {
+  std::lock_guard<std::mutex> lk(g_launch_log_mu);
+  g_launch_log.clear();
+  g_launch_log_on.store(enable ? 1 : 0, std::memory_order_relaxed);
+  return NXEC_OK;
+}
+
+int nxec_debug_launch_log_read(char *buf, int len) {
+  std::lock_guard<std::mutex> lk(g_launch_log_mu);
+  const size_t n = g_launch_log.size();
+  if (buf && len > 0 && n < static_cast<size_t>(len)) {
+    std::memcpy(buf, g_launch_log.data(), n);
+    buf[n] = 0;
+    g_launch_log.clear();
+  }
+  return static_cast<int>(n);
 }
 
 int nxec_describe_launch(nxec_ctx_t *ctx, int rows, int k, int64_t len, int64_t nstripes, char *buf, int buf_len) {

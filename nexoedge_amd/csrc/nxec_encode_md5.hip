@@ -517,6 +517,10 @@ int launch_mul_md5(const MulMd5Args &in, int num_cus, void *stream) {
     lds = 10 * 1024 + static_cast<int>(2 * S * a.p * kEmRow);
   }
 #endif
+  if (launch_log_on())
+    launch_log_append("family=k_mul_md5 k=%d p=%d hsrc=%d hdst=%d copy=%d spg=%d grid=%lld product=%d", a.k, a.p,
+                      a.hash_src != 0, a.hash_dst != 0, a.any_copy != 0, a.stripes_per_group,
+                      static_cast<long long>(grid), fn == kEm[a.hash_src ? 1 : 0][a.k - 1]);
   hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(kEmBlock), lds,
                      static_cast<hipStream_t>(stream), a);
   hipError_t e = hipGetLastError();
@@ -539,6 +543,9 @@ int launch_gather_md5(const GatherMd5Args &in, int num_cus, void *stream) {
   const int64_t grid = (a.nstripes + S - 1) / S;
   if (grid >= (int64_t(1) << 31)) return set_error(NXEC_ERR_INVALID, "gather+md5: batch too large for one launch");
   const int lds = a.k * 1024 + static_cast<int>(2 * S * nh * kEmRow);
+  if (launch_log_on())
+    launch_log_append("family=k_gather_md5 k=%d p=%d hsrc=%d spg=%d grid=%lld", a.k, a.p, a.hash_src != 0,
+                      a.stripes_per_group, static_cast<long long>(grid));
   hipLaunchKernelGGL(kGm[a.hash_src ? 1 : 0][a.k - 1], dim3(static_cast<unsigned>(grid)), dim3(kEmBlock), lds,
                      static_cast<hipStream_t>(stream), a);
   hipError_t e = hipGetLastError();

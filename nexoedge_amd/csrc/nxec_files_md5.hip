@@ -616,6 +616,10 @@ int launch_files_md5(const FilesMd5Args &in, int num_cus, void *stream) {
 #if NXEC_DESIGN_PROBES
   if (tuning().fm_probe >= 0 && a.k == 10 && !a.mask && !a.tail_store) fn = kFmProbe[tuning().fm_probe & 7];
 #endif
+  if (launch_log_on())
+    launch_log_append("family=k_files_md5 k=%d p=%d mask=%d tstore=%d spg=%d grid=%lld product=%d", a.k, a.p,
+                      a.tail_store || a.mask, a.tail_store != 0, a.slots_per_group, static_cast<long long>(grid),
+                      fn == kFm[a.tail_store ? 2 : a.mask ? 1 : 0][a.k - 1]);
   hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(kEmBlock), static_cast<unsigned>(lds),
                      static_cast<hipStream_t>(stream), a);
   hipError_t e = hipGetLastError();

@@ -2,6 +2,7 @@
 #ifndef NXEC_INTERNAL_H
 #define NXEC_INTERNAL_H
 
+#include <atomic>
 #include <cstdint>
 #include <functional>
 #include <vector>
@@ -92,6 +93,12 @@ int launch_mul(const MulArgs &a, bool vec_ok, int num_cus, void *stream);
 int reset_work_queues(void *stream);
 // Testing: stores `next_tile` in the counter of the slot the next launch draws.
 int debug_poison_next_queue_slot(uint32_t next_tile);
+// Testing: the launch record (nxec_debug_launch_log, nxec_context.cpp).  Every
+// kernel launch site tests launch_log_on() -- one relaxed load -- and, when
+// on, appends one "key=value ..." line naming its instantiation (mutex inside).
+extern std::atomic<int> g_launch_log_on;
+inline bool launch_log_on() { return g_launch_log_on.load(std::memory_order_relaxed) != 0; }
+void launch_log_append(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 // Raises the dynamic-LDS limit of every kernel instantiation (once per device).
 int prepare_kernels();
 int launch_fill(void *d, size_t bytes, uint64_t seed, void *stream);

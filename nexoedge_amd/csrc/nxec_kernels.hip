@@ -56,6 +56,19 @@ constexpr int kPermMaxK = 13;  // beyond this the single-row VALU kernel would s
 constexpr int kRingBytes = 16;  // work-queue broadcast ring, after the tables in dynamic LDS
 constexpr bool queue_fits(int table_bytes) { return table_bytes + kRingBytes <= kLdsBytes; }
 
+// Compile-time shape of each instantiation: next-tile prefetch (PF) and work
+// queue (Q).  The kernel templates and the launch record (launch_log_append)
+// both read these, so the record cannot drift from the code that runs.
+constexpr int default_r(int k) { return k <= 9 ? 16 : 8; }
+constexpr bool vec_prefetch(int k, bool copy, bool full) {
+  return k <= ((copy || !full) ? kPrefetchMaxKCopy : kPrefetchMaxK);
+}
+constexpr bool vec_queued(int k, int r) { return queue_fits(k * 1024 * r); }
+constexpr bool perm_prefetch(int k) { return k <= kPermPrefetchMaxK; }
+constexpr bool ragged_prefetch(int k) { return k <= kPrefetchMaxKCopy; }
+// nsrc = data chunks + parity rows of the pass (the tile loader's sources)
+constexpr bool scrub_prefetch(int nsrc, bool full) { return nsrc <= (full ? kPrefetchMaxK : kPrefetchMaxKCopy); }
+
 using dev::build_tables;
 using dev::gf_mul_dev;
 using dev::ld_stream;
@@ -452,8 +465,9 @@ __device__ __forceinline__ void mul_tiles(const MulArgs &a, const Body &body, ui
 
 template <int K, int R, bool GATHER, bool COPY, bool FULL>
 __global__ __launch_bounds__(kBlock) void k_mul_vec(const MulArgs a) {
-  constexpr bool PF = K <= ((COPY || !FULL) ? kPrefetchMaxKCopy : kPrefetchMaxK);
-  constexpr bool Q = queue_fits(LdsBody<K, R, GATHER, COPY>::kLds);
+  constexpr bool PF = vec_prefetch(K, COPY, FULL);
+  constexpr bool Q = vec_queued(K, R);
+  static_assert(LdsBody<K, R, GATHER, COPY>::kLds == K * 1024 * R, "vec_queued() sizes the tables");
   using Body = LdsBody<K, R, GATHER, COPY>;
   extern __shared__ uint32_t tab[];
   Body::setup(a, tab);
@@ -463,7 +477,7 @@ __global__ __launch_bounds__(kBlock) void k_mul_vec(const MulArgs a) {
 
 template <int K, bool GATHER, bool COPY, bool FULL>
 __global__ __launch_bounds__(kBlock) void k_mul_perm(const MulArgs a) {
-  constexpr bool PF = K <= kPermPrefetchMaxK;
+  constexpr bool PF = perm_prefetch(K);
   using Body = PermBody<K, GATHER, COPY>;
   extern __shared__ uint32_t tab[];
   Body::setup(a, tab);
@@ -490,7 +504,7 @@ struct RaggedArgs {
 
 template <int K, int R>
 __global__ __launch_bounds__(kBlock) void k_mul_ragged(const RaggedArgs a) {
-  constexpr bool PF = K <= kPrefetchMaxKCopy;
+  constexpr bool PF = ragged_prefetch(K);
   constexpr int kLds = K * 1024 * R;
   static_assert(queue_fits(kLds), "ragged kernels are queue-driven");
   extern __shared__ uint32_t tab[];
@@ -598,8 +612,8 @@ __global__ __launch_bounds__(256) void k_mul_bytes(const MulArgs a) {
 template <int KD, int ROWS, bool FULL>
 __global__ __launch_bounds__(kBlock) void k_scrub_vec(const ScrubArgs a) {
   constexpr int K = KD + ROWS;
-  constexpr int R = KD <= 9 ? 16 : 8;
-  constexpr bool PF = K <= (FULL ? kPrefetchMaxK : kPrefetchMaxKCopy);
+  constexpr int R = default_r(KD);
+  constexpr bool PF = scrub_prefetch(K, FULL);
   using Body = ScrubBody<KD, ROWS, R>;
   static_assert(K <= kScrubMaxSrc && queue_fits(Body::kLds), "scrub kernels are queue-driven");
   extern __shared__ uint32_t tab[];
@@ -926,7 +940,7 @@ constexpr std::array<ScrubTable, 2> scrub_tables() {
 }
 const std::array<ScrubTable, 2> kScrub[kMaxRowsPerPass] = {scrub_tables<1>(), scrub_tables<2>(), scrub_tables<3>(),
                                                            scrub_tables<4>()};
-int scrub_vec_lds(int k) { return k * 1024 * (k <= 9 ? 16 : 8) + kRingBytes; }
+int scrub_vec_lds(int k) { return k * 1024 * default_r(k) + kRingBytes; }
 
 int hip_fail(hipError_t e, const char *what) {
   return set_error(NXEC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
@@ -942,7 +956,7 @@ int choose_r(int k, bool tunable) {
   // the largest replication that leaves room for the tile-queue ring: the
   // queue's dynamic tile order is worth far more than R = 16's fewer LDS bank
   // conflicts (k = 10: 0.80 vs 0.64-0.73 of 8 TB/s, profiles/r01_mem_pattern.log)
-  return k <= 9 ? 16 : 8;
+  return default_r(k);
 }
 
 KernelFn vec_kernel(int k, int r, bool gather, bool copy, bool full) {
@@ -1112,6 +1126,22 @@ int launch_mul(const MulArgs &a, bool vec_ok, int num_cus, void *stream) {
       const bool is_full = pi == 0;
       LaunchInfo li = plan_launch(b.k, b.rows, b.vec_count, b.nstripes, num_cus, is_full, copy, gather);
       KernelFn fn = li.perm ? kPerm[gather][b.k - 1] : vec_kernel(b.k, li.lds_copies, gather, copy, is_full);
+      if (launch_log_on()) {
+        if (li.perm)
+          launch_log_append("family=k_mul_perm k=%d rows=%d r=0 gather=%d copy=0 full=1 pf=%d q=1 tpg=%u sg=%u "
+                            "grid=%d slot=%d",
+                            b.k, b.rows, gather, perm_prefetch(b.k), b.tiles_per_grab, b.stripe_group, li.grid,
+                            b.queue_slot);
+        else if (b.k > kMaxTemplK)
+          launch_log_append("family=k_mul_vec_dyn k=%d rows=%d r=1 gather=%d copy=%d full=%d pf=0 q=0 tpg=0 sg=1 "
+                            "grid=%d slot=-1",
+                            b.k, b.rows, gather, copy, is_full, li.grid);
+        else
+          launch_log_append("family=k_mul_vec k=%d rows=%d r=%d gather=%d copy=%d full=%d pf=%d q=%d tpg=%u sg=%u "
+                            "grid=%d slot=%d",
+                            b.k, b.rows, li.lds_copies, gather, copy, is_full, vec_prefetch(b.k, copy, is_full),
+                            vec_queued(b.k, li.lds_copies), b.tiles_per_grab, b.stripe_group, li.grid, b.queue_slot);
+      }
       hipLaunchKernelGGL(fn, dim3(li.grid), dim3(li.block), li.lds_bytes, st, b);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return launch_failed(e, "launch k_mul_vec", b.queue_slot, st);
@@ -1122,6 +1152,11 @@ int launch_mul(const MulArgs &a, bool vec_ok, int num_cus, void *stream) {
     int64_t blocks = (total + 255) / 256;
     if (blocks > static_cast<int64_t>(num_cus) * 8) blocks = static_cast<int64_t>(num_cus) * 8;
     KernelFn fn = a.src_ptrs ? &k_mul_bytes<true> : &k_mul_bytes<false>;
+    if (launch_log_on())
+      launch_log_append("family=k_mul_bytes k=%d rows=%d r=1 gather=%d copy=%d full=0 pf=0 q=0 tpg=0 sg=1 grid=%lld "
+                        "byte_begin=%lld",
+                        a.k, a.rows, a.src_ptrs != nullptr, a.any_copy != 0, static_cast<long long>(blocks),
+                        static_cast<long long>(a.byte_begin));
     hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(blocks)), dim3(256), a.k * 1024, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch k_mul_bytes");
@@ -1162,6 +1197,10 @@ int launch_scrub_detect(const ScrubArgs &a0, bool vec_ok, int num_cus, void *str
       b.m.vec_count = parts[pi][1];
       const int64_t ntiles = (b.m.vec_count + kBlock - 1) / kBlock * b.m.nstripes;
       const int64_t grid = std::min<int64_t>(num_cus, ntiles);
+      if (launch_log_on())
+        launch_log_append("family=k_scrub_vec kd=%d rows=%d r=%d full=%d pf=%d q=1 tpg=%u sg=%u grid=%lld slot=%d", m.k,
+                          m.rows, default_r(m.k), pi == 0, scrub_prefetch(m.k + m.rows, pi == 0), b.m.tiles_per_grab,
+                          b.m.stripe_group, static_cast<long long>(grid), b.m.queue_slot);
       hipLaunchKernelGGL(kScrub[m.rows - 1][pi == 0][m.k - 1], dim3(static_cast<unsigned>(grid)), dim3(kBlock),
                          scrub_vec_lds(m.k), st, b);
       hipError_t e = hipGetLastError();
@@ -1172,6 +1211,9 @@ int launch_scrub_detect(const ScrubArgs &a0, bool vec_ok, int num_cus, void *str
     const int64_t total = (m.len - m.byte_begin) * m.nstripes;
     int64_t blocks = (total + 255) / 256;
     if (blocks > static_cast<int64_t>(num_cus) * 8) blocks = static_cast<int64_t>(num_cus) * 8;
+    if (launch_log_on())
+      launch_log_append("family=k_scrub_bytes kd=%d rows=%d grid=%lld byte_begin=%lld", m.k, m.rows,
+                        static_cast<long long>(blocks), static_cast<long long>(m.byte_begin));
     hipLaunchKernelGGL(k_scrub_bytes, dim3(static_cast<unsigned>(blocks)), dim3(256), m.k * 1024, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch k_scrub_bytes");
@@ -1225,6 +1267,8 @@ int launch_mul_list(int rows, int k, const uint8_t *coeffs, const ListStripe *d_
     a.row0 = r0;
     for (int r = 0; r < a.rows; r++)
       for (int j = 0; j < k; j++) a.coef[r * k + j] = coeffs[static_cast<size_t>(r0 + r) * k + j];
+    if (launch_log_on())
+      launch_log_append("family=k_mul_list k=%d rows=%d grid=%lld", k, a.rows, static_cast<long long>(blocks));
     hipLaunchKernelGGL(k_mul_list, dim3(static_cast<unsigned>(blocks)), dim3(256), k * 1024,
                        static_cast<hipStream_t>(stream), a);
     hipError_t e = hipGetLastError();
@@ -1236,10 +1280,10 @@ int launch_mul_list(int rows, int k, const uint8_t *coeffs, const ListStripe *d_
 using RaggedFn = void (*)(RaggedArgs);
 template <int... Ks>
 constexpr std::array<RaggedFn, sizeof...(Ks)> ragged_table(std::integer_sequence<int, Ks...>) {
-  return {{&k_mul_ragged<Ks + 1, (Ks + 1 <= 9 ? 16 : 8)>...}};
+  return {{&k_mul_ragged<Ks + 1, default_r(Ks + 1)>...}};
 }
 const std::array<RaggedFn, kMaxRaggedK> kRagged = ragged_table(std::make_integer_sequence<int, kMaxRaggedK>{});
-int ragged_lds(int k) { return k * 1024 * (k <= 9 ? 16 : 8) + kRingBytes; }
+int ragged_lds(int k) { return k * 1024 * default_r(k) + kRingBytes; }
 
 int launch_mul_ragged(int rows, int k, const uint8_t *coeffs, const ListStripe *d_stripes, const uint32_t *d_tile_stripe,
                       const uint32_t *d_stripe_tile0, int64_t ntiles, int num_cus, void *stream) {
@@ -1269,6 +1313,9 @@ int launch_mul_ragged(int rows, int k, const uint8_t *coeffs, const ListStripe *
     a.tiles_per_grab = std::max(1, std::min(8, (12 + k + a.rows - 1) / (k + a.rows)));
     for (int r = 0; r < a.rows; r++)
       for (int j = 0; j < k; j++) a.coef[r * k + j] = coeffs[static_cast<size_t>(r0 + r) * k + j];
+    if (launch_log_on())
+      launch_log_append("family=k_mul_ragged k=%d rows=%d r=%d pf=%d q=1 tpg=%u grid=%lld slot=%d", k, a.rows,
+                        default_r(k), ragged_prefetch(k), a.tiles_per_grab, static_cast<long long>(grid), a.queue_slot);
     hipLaunchKernelGGL(kRagged[k - 1], dim3(static_cast<unsigned>(grid)), dim3(kBlock), ragged_lds(k),
                        static_cast<hipStream_t>(stream), a);
     hipError_t e = hipGetLastError();

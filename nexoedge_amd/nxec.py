@@ -286,6 +286,28 @@ def default_pick(inflight: Sequence[int], nodes: Optional[Sequence[int]] = None,
     return r
 
 
+def launch_log(enable: bool = True) -> None:
+    """nxec_debug_launch_log: turn the process-wide launch record on or off (either clears it)."""
+    check(lib.nxec_debug_launch_log(int(bool(enable))), "nxec_debug_launch_log")
+
+
+def launch_log_read() -> list:
+    """nxec_debug_launch_log_read: the launches recorded since the last read, one dict per launch
+    (field values are ints except `family`); the record is cleared."""
+    size = 1 << 16
+    while True:
+        buf = C.create_string_buffer(size)
+        n = lib.nxec_debug_launch_log_read(buf, size)
+        if n < size:
+            break
+        size = n + 1
+    out = []
+    for line in buf.value.decode().splitlines():
+        rec = dict(f.split("=", 1) for f in line.split())
+        out.append({key: (v if key == "family" else int(v)) for key, v in rec.items()})
+    return out
+
+
 def set_device(dev: int) -> None:
     """nxec_set_device: make `dev` the calling thread's current device (its
     allocations, e.g. DeviceBuffer, land there)."""

@@ -374,6 +374,25 @@ static void default_pool(int t) {
   }
 }
 
+// The launch record (nxec_debug_launch_log): writers, a reader and the on/off
+// switch from 8 threads at once; every line read back is whole.
+static void launch_record(int t) {
+  char buf[8192];
+  for (int it = 0; it < 400; it++) {
+    if (nxec::launch_log_on()) nxec::launch_log_append("family=k_test k=%d rows=%d grid=%d", t, it % 4, it);
+    if (t == 0 && it % 50 == 25) CHECK(nxec_debug_launch_log(it % 100 == 25) == NXEC_OK, "switch");
+    if (t == 1 && it % 7 == 0) {
+      const int n = nxec_debug_launch_log_read(buf, sizeof buf);
+      CHECK(n >= 0, "read");
+      if (n > 0 && n < static_cast<int>(sizeof buf)) {
+        CHECK(static_cast<int>(std::strlen(buf)) == n && buf[n - 1] == '\n', "record is NUL terminated whole lines");
+        for (const char *l = buf; *l; l = std::strchr(l, '\n') + 1)
+          CHECK(std::strncmp(l, "family=k_test k=", 16) == 0, "torn line");
+      }
+    }
+  }
+}
+
 int main() {
   gf_and_planning();
   files_slot_plan();
@@ -390,6 +409,23 @@ int main() {
   std::vector<std::thread> pt;
   for (int t = 0; t < 8; t++) pt.emplace_back(default_pool, t);
   for (auto &t : pt) t.join();
+  {
+    char small[4];
+    CHECK(nxec_debug_launch_log_read(small, sizeof small) == 0, "the record is empty and off by default");
+    CHECK(nxec_debug_launch_log(1) == NXEC_OK, "record on");
+    std::vector<std::thread> lt;
+    for (int t = 0; t < 8; t++) lt.emplace_back(launch_record, t);
+    for (auto &t : lt) t.join();
+    CHECK(nxec_debug_launch_log(1) == NXEC_OK, "record on (clears)");
+    nxec::launch_log_append("family=k_test k=%d", 7);
+    CHECK(nxec_debug_launch_log_read(small, sizeof small) == 18, "too small a buffer: the length, nothing consumed");
+    char line[64];
+    CHECK(nxec_debug_launch_log_read(line, sizeof line) == 18 && std::strcmp(line, "family=k_test k=7\n") == 0, "read");
+    CHECK(nxec_debug_launch_log_read(line, sizeof line) == 0, "a read clears the record");
+    CHECK(nxec_debug_launch_log(0) == NXEC_OK, "record off");
+    nxec::launch_log_append("family=k_test k=%d", 8);
+    CHECK(nxec_debug_launch_log_read(line, sizeof line) == 0, "nothing recorded while off");
+  }
   // every lease released: nothing left in flight
   {
     int dv[16], nd[16], inf[16], cnt = 0;
