@@ -58,7 +58,7 @@ __device__ __forceinline__ uint32_t byte_x4(uint32_t w) {
 // one SDWA address op per byte, the source's table offset as the ds_read
 // immediate, one v_bitop3 (3-way XOR) per two lookups.  The tables are the
 // first bytes of the dynamic LDS and the kernel has no static LDS
-// (prepare_encode_md5 checks), so an integer LDS address is the table offset.
+// (raise_lds checks), so an integer LDS address is the table offset.
 typedef __attribute__((address_space(3))) const uint32_t lds_u32;
 __device__ __forceinline__ uint32_t ent(int table_off, uint32_t byte_off) {
   return *reinterpret_cast<lds_u32 *>(static_cast<uintptr_t>(byte_off + table_off));
@@ -448,6 +448,6 @@ constexpr int gm_depth() {
 
 // k_mul_md5_ring (nxec_encode_md5_ring.hip) for (hash_src, k), and its kernel attributes
 void (*mul_md5_ring_kernel(bool hash_src, int k))(const MulMd5Args);
-int prepare_encode_md5_ring();
+void list_encode_md5_ring_kernels(std::vector<KernelLds> &out);
 
 }  // namespace nxec

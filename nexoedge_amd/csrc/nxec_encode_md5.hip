@@ -431,47 +431,19 @@ bool mul_md5_eligible(int k, int rows, int64_t len, const void *src, int64_t src
   return (bits & 15) == 0;
 }
 
-int prepare_encode_md5() {
+// The fused kernels ask for up to the whole LDS, and their tables must start
+// at LDS byte 0 (nxec_em_common.h): the per-device pass refuses static LDS.
+void list_encode_md5_kernels(std::vector<KernelLds> &out) {
+  for (const auto &t : kEm)
+    for (EmKernel fn : t) out.push_back({reinterpret_cast<const void *>(fn), "k_mul_md5", kEmLds, true});
+  for (const auto &t : kGm)
+    for (GmKernel fn : t) out.push_back({reinterpret_cast<const void *>(fn), "k_gather_md5", kEmLds, true});
 #if NXEC_DESIGN_PROBES
-  if (int rc = prepare_encode_md5_ring()) return rc;
+  list_encode_md5_ring_kernels(out);
+  out.push_back({reinterpret_cast<const void *>(kEmNib), "k_mul_md5 nib", kEmLds, false});
+  out.push_back({reinterpret_cast<const void *>(kEmHg), "k_mul_md5 hg", kEmLds, false});
+  for (EmKernel fn : kEmProbe) out.push_back({reinterpret_cast<const void *>(fn), "k_mul_md5 probe", kEmLds, false});
 #endif
-  for (int i = 0; i < 2 * kEncMd5MaxK; i++) {
-    const EmKernel fn = kEm[i / kEncMd5MaxK][i % kEncMd5MaxK];
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(fn)) != hipSuccess || fa.sharedSizeBytes != 0)
-      return set_error(NXEC_ERR_HIP, "k_mul_md5: static LDS present (the tables must start at LDS byte 0)");
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kEmLds);
-    if (e != hipSuccess) return set_error(NXEC_ERR_HIP, "hipFuncSetAttribute(k_mul_md5): %s", hipGetErrorString(e));
-  }
-  if (int rc = prepare_files_md5()) return rc;
-  for (GmKernel fn : kGm[0]) {
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(fn)) != hipSuccess || fa.sharedSizeBytes != 0)
-      return set_error(NXEC_ERR_HIP, "k_gather_md5: static LDS present (the tables must start at LDS byte 0)");
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, kEmLds);
-    if (e != hipSuccess) return set_error(NXEC_ERR_HIP, "hipFuncSetAttribute(k_gather_md5): %s", hipGetErrorString(e));
-  }
-  for (GmKernel fn : kGm[1]) {
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(fn)) != hipSuccess || fa.sharedSizeBytes != 0)
-      return set_error(NXEC_ERR_HIP, "k_gather_md5: static LDS present (the tables must start at LDS byte 0)");
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, kEmLds);
-    if (e != hipSuccess) return set_error(NXEC_ERR_HIP, "hipFuncSetAttribute(k_gather_md5): %s", hipGetErrorString(e));
-  }
-#if NXEC_DESIGN_PROBES
-  {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kEmNib), hipFuncAttributeMaxDynamicSharedMemorySize, kEmLds);
-    if (e != hipSuccess) return set_error(NXEC_ERR_HIP, "hipFuncSetAttribute(k_mul_md5 nib): %s", hipGetErrorString(e));
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kEmHg), hipFuncAttributeMaxDynamicSharedMemorySize, kEmLds);
-    if (e != hipSuccess) return set_error(NXEC_ERR_HIP, "hipFuncSetAttribute(k_mul_md5 hg): %s", hipGetErrorString(e));
-  }
-  for (EmKernel fn : kEmProbe) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, kEmLds);
-    if (e != hipSuccess) return set_error(NXEC_ERR_HIP, "hipFuncSetAttribute(k_mul_md5 probe): %s", hipGetErrorString(e));
-  }
-#endif
-  return NXEC_OK;
 }
 
 int launch_mul_md5(const MulMd5Args &in, int num_cus, void *stream) {

@@ -219,16 +219,9 @@ const std::array<EmKernel, kEncMd5MaxK> kEmRing[2] = {
 
 void (*mul_md5_ring_kernel(bool hash_src, int k))(const MulMd5Args) { return kEmRing[hash_src ? 1 : 0][k - 1]; }
 
-int prepare_encode_md5_ring() {
-  for (int i = 0; i < 2 * kEncMd5MaxK; i++) {
-    const EmKernel fn = kEmRing[i / kEncMd5MaxK][i % kEncMd5MaxK];
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(fn)) != hipSuccess || fa.sharedSizeBytes != 0)
-      return set_error(NXEC_ERR_HIP, "k_mul_md5_ring: static LDS present (the tables must start at LDS byte 0)");
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, kEmLds);
-    if (e != hipSuccess) return set_error(NXEC_ERR_HIP, "hipFuncSetAttribute(k_mul_md5_ring): %s", hipGetErrorString(e));
-  }
-  return NXEC_OK;
+void list_encode_md5_ring_kernels(std::vector<KernelLds> &out) {
+  for (const auto &t : kEmRing)
+    for (EmKernel fn : t) out.push_back({reinterpret_cast<const void *>(fn), "k_mul_md5_ring", kEmLds, true});
 }
 
 }  // namespace nxec

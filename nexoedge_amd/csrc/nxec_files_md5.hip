@@ -488,22 +488,12 @@ const FmKernel kFmProbe[8] = {&k_files_md5<10, 0>, &k_files_md5<10, 1>, &k_files
 
 }  // namespace
 
-int prepare_files_md5() {
-  for (int t = 0; t < 3 * kFilesMd5MaxK; t++) {
-    const FmKernel fn = kFm[t / kFilesMd5MaxK][t % kFilesMd5MaxK];
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(fn)) != hipSuccess || fa.sharedSizeBytes != 0)
-      return set_error(NXEC_ERR_HIP, "k_files_md5: static LDS present (the tables must start at LDS byte 0)");
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, kEmLds);
-    if (e != hipSuccess) return set_error(NXEC_ERR_HIP, "hipFuncSetAttribute(k_files_md5): %s", hipGetErrorString(e));
-  }
+void list_files_md5_kernels(std::vector<KernelLds> &out) {
+  for (const auto &t : kFm)
+    for (FmKernel fn : t) out.push_back({reinterpret_cast<const void *>(fn), "k_files_md5", kEmLds, true});
 #if NXEC_DESIGN_PROBES
-  for (FmKernel fn : kFmProbe) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, kEmLds);
-    if (e != hipSuccess) return set_error(NXEC_ERR_HIP, "hipFuncSetAttribute(k_files_md5 probe): %s", hipGetErrorString(e));
-  }
+  for (FmKernel fn : kFmProbe) out.push_back({reinterpret_cast<const void *>(fn), "k_files_md5 probe", kEmLds, false});
 #endif
-  return NXEC_OK;
 }
 
 void plan_files_slots(const std::vector<int64_t> &lens, int k, int p, int num_cus, std::vector<int32_t> &slot_first,

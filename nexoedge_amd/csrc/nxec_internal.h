@@ -2,6 +2,7 @@
 #ifndef NXEC_INTERNAL_H
 #define NXEC_INTERNAL_H
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <functional>
@@ -88,6 +89,8 @@ LaunchInfo plan_launch(int k, int rows, int64_t vec_count, int64_t nstripes, int
                        bool gather);
 // Enqueues one pass (vector kernel + byte kernel for tails / misaligned data).
 int launch_mul(const MulArgs &a, bool vec_ok, int num_cus, void *stream);
+// The vector kernel launch_mul runs for the pass li = plan_launch(k, ...) describes.
+void (*mul_kernel(const LaunchInfo &li, int k, bool gather, bool copy, bool full))(MulArgs);
 // Zeroes every tile-queue slot of the current device (stream-ordered, then
 // synchronised); for recovery after a device error.
 int reset_work_queues(void *stream);
@@ -99,7 +102,27 @@ int debug_poison_next_queue_slot(uint32_t next_tile);
 extern std::atomic<int> g_launch_log_on;
 inline bool launch_log_on() { return g_launch_log_on.load(std::memory_order_relaxed) != 0; }
 void launch_log_append(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-// Raises the dynamic-LDS limit of every kernel instantiation (once per device).
+// The most stripes of vec_count 16-byte vectors per chunk that one launch
+// takes: its count of 1024-vector tiles has to fit 32 bits (callers split nstripes).
+inline int64_t max_stripes_per_launch(int64_t vec_count) {
+  const int64_t tps = std::max<int64_t>(1, (vec_count + 1023) / 1024);
+  return std::max<int64_t>(1, (int64_t(1) << 31) / tps);
+}
+// Per-device preparation.  kernel_lds_list() holds one entry per kernel
+// instantiation that takes dynamic LDS, collected once by walking the dispatch
+// tables of nxec_kernels.hip, nxec_encode_md5.hip and nxec_files_md5.hip (each
+// file appends its own); prepare_kernels() calls raise_lds() on every entry,
+// once per device (ensure_device).
+struct KernelLds {
+  const void *fn;
+  const char *family;  // names the kernel in error texts
+  int bytes;           // the most dynamic LDS a launch of it asks for
+  bool no_static;      // its tables start at LDS byte 0: static LDS is an error
+};
+const std::vector<KernelLds> &kernel_lds_list();
+void list_encode_md5_kernels(std::vector<KernelLds> &out);
+void list_files_md5_kernels(std::vector<KernelLds> &out);
+int raise_lds(const void *fn, int bytes, const char *family, bool no_static = false);
 int prepare_kernels();
 int launch_fill(void *d, size_t bytes, uint64_t seed, void *stream);
 // 16-byte-aligned copy by a kernel (dst may be device-mapped pinned host memory:
@@ -142,6 +165,8 @@ struct ScrubArgs {
   uint32_t par_off[kMaxRowsPerPass];
 };
 bool scrub_vec_shape(int k, int rows);
+// The vector kernel of a scrub_vec_shape() pass and the dynamic LDS its launch asks for.
+void (*scrub_kernel(int kd, int rows, bool full, int *lds_bytes))(ScrubArgs);
 int launch_scrub_detect(const ScrubArgs &a, bool vec_ok, int num_cus, void *stream);
 // Locate / heal stage: workgroup s leaves at once unless status[s] != CLEAN;
 // counts the stripe into *nbad (optional); with NXEC_SCRUB_LOCATE recomputes
@@ -173,6 +198,8 @@ int launch_mul_list(int rows, int k, const uint8_t *coeffs, const ListStripe *d_
 // through the work-queue LDS-table kernel; tile t is column tile
 // t - stripe_tile0[s] of stripe s = tile_stripe[t] (1024 16-byte vectors each).
 constexpr int kMaxRaggedK = 19;
+// The ragged kernel of k <= kMaxRaggedK and the dynamic LDS its launch asks for.
+const void *ragged_kernel(int k, int *lds_bytes);
 int launch_mul_ragged(int rows, int k, const uint8_t *coeffs, const ListStripe *d_stripes, const uint32_t *d_tile_stripe,
                       const uint32_t *d_stripe_tile0, int64_t ntiles, int num_cus, void *stream);
 // Last stripe of an object into the aligned tail arena: dst + j*cls (j < k)
@@ -188,13 +215,6 @@ struct PadChunks {
 };
 int launch_pad_chunks(const PadChunks *d_items, const uint32_t *d_bstart, int64_t nitems, int64_t nblocks,
                       void *stream);
-// copy item i: dst[0 .. dst_len) = src[0 .. src_len) then zeros (src_len <= dst_len)
-struct PadCopy {
-  const uint8_t *src;
-  uint8_t *dst;
-  int64_t src_len, dst_len;
-};
-int launch_pad_copy(const PadCopy *d_items, int64_t nitems, void *stream);
 // MD5 of a list of chunks: digest of p[0 .. len) to `digest`
 struct Md5Item {
   const uint8_t *p;
@@ -246,9 +266,6 @@ struct MulMd5Args {
 bool mul_md5_eligible(int k, int rows, int64_t len, const void *src, int64_t src_stripe_stride, const uint32_t *src_off,
                       const void *dst, int64_t dst_stripe_stride, const uint32_t *dst_off,
                       const uint32_t *copy_off = nullptr);
-int prepare_encode_md5();
-// k_files_md5's kernel attributes (nxec_files_md5.hip; called by prepare_encode_md5)
-int prepare_files_md5();
 int launch_mul_md5(const MulMd5Args &a, int num_cus, void *stream);
 
 // The agent's form of the fused kernel (nxec_agent_encode_batch): request s

@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <utility>
@@ -63,7 +64,17 @@ constexpr int default_r(int k) { return k <= 9 ? 16 : 8; }
 constexpr bool vec_prefetch(int k, bool copy, bool full) {
   return k <= ((copy || !full) ? kPrefetchMaxKCopy : kPrefetchMaxK);
 }
-constexpr bool vec_queued(int k, int r) { return queue_fits(k * 1024 * r); }
+// Dynamic LDS of each kernel family, computed here and nowhere else: the
+// kernels' static_asserts, the per-device preparation (list_kernels) and the
+// launches all call these.  r copies of k 256-entry tables, then the queue
+// ring where it fits (the scrub and ragged kernels exist only where it does).
+constexpr int table_bytes(int k, int r) { return k * 1024 * r; }
+constexpr bool vec_queued(int k, int r) { return queue_fits(table_bytes(k, r)); }
+constexpr int vec_lds(int k, int r) { return table_bytes(k, r) + (vec_queued(k, r) ? kRingBytes : 0); }
+constexpr int scrub_vec_lds(int kd) { return vec_lds(kd, default_r(kd)); }
+constexpr int ragged_lds(int k) { return vec_lds(k, default_r(k)); }
+constexpr int perm_lds(int k) { return k * 32 + kRingBytes; }
+constexpr int bytes_lds(int k) { return table_bytes(k, 1); }  // k_mul_vec_dyn, k_mul_bytes, k_scrub_bytes, k_mul_list
 constexpr bool perm_prefetch(int k) { return k <= kPermPrefetchMaxK; }
 constexpr bool ragged_prefetch(int k) { return k <= kPrefetchMaxKCopy; }
 // nsrc = data chunks + parity rows of the pass (the tile loader's sources)
@@ -98,24 +109,33 @@ __device__ __forceinline__ const uint8_t *src_chunk(const MulArgs &a, uint32_t s
 
 // acc[p] holds the 4 row products of column byte p (p = 4q + b); write row r's
 // 16 bytes = byte r of acc[0..15].  8 v_perm_b32 per 4 columns.
-template <bool GATHER>
-__device__ __forceinline__ void store_rows(const MulArgs &a, uint32_t s, uint32_t v, const uint32_t acc[16]) {
-  uint32_t o[4][4];
-  rows_of(acc, o);
-#pragma unroll
-  for (int r = 0; r < kMaxRowsPerPass; r++) {
-    if (r < a.rows) st_stream(dst_row<GATHER>(a, s, r) + static_cast<size_t>(v) * 16, u32x4{o[r][0], o[r][1], o[r][2], o[r][3]});
-  }
-}
-
-// the same transpose, row r (< rows) stored at row0 + r*row_stride + v*16
-__device__ __forceinline__ void store_rows_ptr(uint8_t *row0, int64_t row_stride, int rows, uint32_t v,
-                                               const uint32_t acc[16]) {
+// Row r (< rows) goes to row(r), the address of this lane's 16 bytes of it.
+// `rows` is read at each use and the callers' lambdas capture by value: the
+// generated code is then that of the loop written out in each kernel (a row
+// count read ahead of the loop, or by-reference captures, move k_mul_vec's and
+// k_mul_ragged's register counts).
+template <class RowF>
+__device__ __forceinline__ void store_rows(const uint32_t acc[16], const int &rows, RowF row) {
   uint32_t o[4][4];
   rows_of(acc, o);
 #pragma unroll
   for (int r = 0; r < kMaxRowsPerPass; r++)
-    if (r < rows) st_stream(row0 + r * row_stride + static_cast<size_t>(v) * 16, u32x4{o[r][0], o[r][1], o[r][2], o[r][3]});
+    if (r < rows) st_stream(row(r), u32x4{o[r][0], o[r][1], o[r][2], o[r][3]});
+}
+template <bool GATHER>
+__device__ __forceinline__ void store_rows(const MulArgs &a, uint32_t s, uint32_t v, const uint32_t acc[16]) {
+  store_rows(acc, a.rows, [&a, s, v](int r) { return dst_row<GATHER>(a, s, r) + static_cast<size_t>(v) * 16; });
+}
+
+// acc = the packed row products of this lane's column, XORed over the first N
+// sources of d; tlane = this lane's copy of source 0's table.
+template <int N, int R, int K>
+__device__ __forceinline__ void lookup_sources(const char *tlane, const u32x4 (&d)[K], uint32_t (&acc)[16]) {
+  static_assert(N <= K, "N of the K loaded sources");
+#pragma unroll
+  for (int i = 0; i < 16; i++) acc[i] = 0;
+#pragma unroll
+  for (int j = 0; j < N; j++) lookup16<R>(tlane + j * table_bytes(1, R), d[j], acc);
 }
 
 // Column vector v (relative to the launch's vec_begin) of stripe s for tile t;
@@ -165,17 +185,14 @@ __device__ __forceinline__ void copy_through(const MulArgs &a, uint32_t s, uint3
 // --- algorithm 1: LDS product tables (any rows <= 4) ---
 template <int K, int R, bool GATHER, bool COPY>
 struct LdsBody {
-  static constexpr int kLds = K * 1024 * R;
+  static constexpr int kLds = table_bytes(K, R);
   static __device__ __forceinline__ void setup(const MulArgs &a, uint32_t *tab) { build_tables<R>(a, K, tab); }
   const char *tlane;
   __device__ explicit LdsBody(const uint32_t *tab)
       : tlane(reinterpret_cast<const char *>(tab) + (threadIdx.x % R) * 4) {}
   __device__ __forceinline__ void operator()(const MulArgs &a, uint32_t s, uint32_t vg, const u32x4 (&d)[K]) const {
     uint32_t acc[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) acc[i] = 0;
-#pragma unroll
-    for (int j = 0; j < K; j++) lookup16<R>(tlane + j * 1024 * R, d[j], acc);
+    lookup_sources<K, R>(tlane, d, acc);
     store_rows<GATHER>(a, s, vg, acc);
     copy_through<K, COPY>(a, s, vg, d);
   }
@@ -195,7 +212,7 @@ __device__ __forceinline__ void scrub_flag(int32_t *status, uint32_t s) {
 template <int KD, int ROWS, int R>
 struct ScrubBody {
   static constexpr int K = KD + ROWS;
-  static constexpr int kLds = KD * 1024 * R;
+  static constexpr int kLds = table_bytes(KD, R);
   static __device__ __forceinline__ void setup(const MulArgs &a, uint32_t *tab) {
     build_tables<R>(a.coef, KD, ROWS, tab);
   }
@@ -205,10 +222,7 @@ struct ScrubBody {
       : tlane(reinterpret_cast<const char *>(tab) + (threadIdx.x % R) * 4), status(st) {}
   __device__ __forceinline__ void operator()(const MulArgs &, uint32_t s, uint32_t, const u32x4 (&d)[K]) const {
     uint32_t acc[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) acc[i] = 0;
-#pragma unroll
-    for (int j = 0; j < KD; j++) lookup16<R>(tlane + j * 1024 * R, d[j], acc);
+    lookup_sources<KD, R>(tlane, d, acc);
     uint32_t o[4][4];
     rows_of(acc, o);
     uint32_t bad = 0;
@@ -467,8 +481,8 @@ template <int K, int R, bool GATHER, bool COPY, bool FULL>
 __global__ __launch_bounds__(kBlock) void k_mul_vec(const MulArgs a) {
   constexpr bool PF = vec_prefetch(K, COPY, FULL);
   constexpr bool Q = vec_queued(K, R);
-  static_assert(LdsBody<K, R, GATHER, COPY>::kLds == K * 1024 * R, "vec_queued() sizes the tables");
   using Body = LdsBody<K, R, GATHER, COPY>;
+  static_assert(Body::kLds + (Q ? kRingBytes : 0) == vec_lds(K, R), "tables, then the ring: what the launch asks for");
   extern __shared__ uint32_t tab[];
   Body::setup(a, tab);
   __syncthreads();
@@ -479,6 +493,7 @@ template <int K, bool GATHER, bool COPY, bool FULL>
 __global__ __launch_bounds__(kBlock) void k_mul_perm(const MulArgs a) {
   constexpr bool PF = perm_prefetch(K);
   using Body = PermBody<K, GATHER, COPY>;
+  static_assert(Body::kLds + kRingBytes == perm_lds(K), "tables, then the ring: what the launch asks for");
   extern __shared__ uint32_t tab[];
   Body::setup(a, tab);
   __syncthreads();
@@ -505,8 +520,8 @@ struct RaggedArgs {
 template <int K, int R>
 __global__ __launch_bounds__(kBlock) void k_mul_ragged(const RaggedArgs a) {
   constexpr bool PF = ragged_prefetch(K);
-  constexpr int kLds = K * 1024 * R;
-  static_assert(queue_fits(kLds), "ragged kernels are queue-driven");
+  constexpr int kLds = table_bytes(K, R);
+  static_assert(R == default_r(K) && kLds + kRingBytes == ragged_lds(K), "ragged kernels are queue-driven");
   extern __shared__ uint32_t tab[];
   build_tables<R>(a.coef, K, a.rows, tab);
   __syncthreads();
@@ -531,11 +546,10 @@ __global__ __launch_bounds__(kBlock) void k_mul_ragged(const RaggedArgs a) {
     where(t, st, v);
     if (v * int64_t(16) < st.len) {
       uint32_t acc[16];
-#pragma unroll
-      for (int i = 0; i < 16; i++) acc[i] = 0;
-#pragma unroll
-      for (int j = 0; j < K; j++) lookup16<R>(tl + j * 1024 * R, d[j], acc);
-      store_rows_ptr(st.dst + a.row0 * st.dst_cs, st.dst_cs, a.rows, v, acc);
+      lookup_sources<K, R>(tl, d, acc);
+      uint8_t *row0 = st.dst + a.row0 * st.dst_cs;
+      const int rows = a.rows;
+      store_rows(acc, rows, [=](int r) { return row0 + r * st.dst_cs + static_cast<size_t>(v) * 16; });
     }
   };
   // wave 0 (lane 0 = the tile's first vector) always issues its K loads
@@ -615,7 +629,7 @@ __global__ __launch_bounds__(kBlock) void k_scrub_vec(const ScrubArgs a) {
   constexpr int R = default_r(KD);
   constexpr bool PF = scrub_prefetch(K, FULL);
   using Body = ScrubBody<KD, ROWS, R>;
-  static_assert(K <= kScrubMaxSrc && queue_fits(Body::kLds), "scrub kernels are queue-driven");
+  static_assert(K <= kScrubMaxSrc && Body::kLds + kRingBytes == scrub_vec_lds(KD), "scrub kernels are queue-driven");
   extern __shared__ uint32_t tab[];
   Body::setup(a.m, tab);
   __syncthreads();
@@ -761,11 +775,7 @@ __global__ __launch_bounds__(256) void k_mul_list(const ListArgs a) {
 #pragma unroll
       for (int i = 0; i < 16; i++) acc[i] = 0;
       for (int j = 0; j < k; j++) lookup16<1>(tl + j * 1024, ld_stream(st.src + j * st.src_cs + off), acc);
-      uint32_t o[4][4];
-      rows_of(acc, o);
-#pragma unroll
-      for (int r = 0; r < kMaxRowsPerPass; r++)
-        if (r < a.rows) st_stream(drow0 + r * st.dst_cs, u32x4{o[r][0], o[r][1], o[r][2], o[r][3]});
+      store_rows(acc, a.rows, [=](int r) { return drow0 + r * st.dst_cs; });
     } else {
       for (int b = 0; b < nb; b++) {
         uint32_t acc = 0;
@@ -774,17 +784,6 @@ __global__ __launch_bounds__(256) void k_mul_list(const ListArgs a) {
       }
     }
   }
-}
-
-// zero-padded copies (the last stripe of each object, chunk_manager.cc:390-399);
-// blockIdx.y-less: item = blockIdx.x / kPadParts, each part a slice of it
-constexpr int kPadParts = 8;
-__global__ __launch_bounds__(256) void k_pad_copy(const PadCopy *items) {
-  const PadCopy it = items[blockIdx.x / kPadParts];
-  const int part = blockIdx.x % kPadParts;
-  const int64_t per = ((it.dst_len + kPadParts - 1) / kPadParts + 15) / 16 * 16;
-  const int64_t b0 = part * per, b1 = b0 + per < it.dst_len ? b0 + per : it.dst_len;
-  for (int64_t i = b0 + threadIdx.x; i < b1; i += blockDim.x) it.dst[i] = i < it.src_len ? it.src[i] : 0;
 }
 
 // Last stripe of an object into the aligned tail arena: chunk j of the
@@ -940,7 +939,13 @@ constexpr std::array<ScrubTable, 2> scrub_tables() {
 }
 const std::array<ScrubTable, 2> kScrub[kMaxRowsPerPass] = {scrub_tables<1>(), scrub_tables<2>(), scrub_tables<3>(),
                                                            scrub_tables<4>()};
-int scrub_vec_lds(int k) { return k * 1024 * default_r(k) + kRingBytes; }
+
+using RaggedFn = void (*)(RaggedArgs);
+template <int... Ks>
+constexpr std::array<RaggedFn, sizeof...(Ks)> ragged_table(std::integer_sequence<int, Ks...>) {
+  return {{&k_mul_ragged<Ks + 1, default_r(Ks + 1)>...}};
+}
+const std::array<RaggedFn, kMaxRaggedK> kRagged = ragged_table(std::make_integer_sequence<int, kMaxRaggedK>{});
 
 int hip_fail(hipError_t e, const char *what) {
   return set_error(NXEC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
@@ -966,11 +971,33 @@ KernelFn vec_kernel(int k, int r, bool gather, bool copy, bool full) {
   return kDefR8[gather][copy][full][k - 1];
 }
 
+// Appends every non-null entry of a dispatch table (indexed by k - 1) to the
+// preparation list; bytes(k) is the family's size function.
+template <class Table, class BytesF>
+void list_table(std::vector<KernelLds> &out, const Table &table, const char *family, const BytesF &bytes) {
+  int k = 0;
+  for (auto fn : table) {
+    k++;
+    if (fn) out.push_back({reinterpret_cast<const void *>(fn), family, bytes(k), false});
+  }
+}
 
-// dynamic LDS of a k_mul_vec instantiation: tables (+ the queue ring where it fits)
-int table_lds(int k, int r) {
-  const int t = k * 1024 * r;
-  return queue_fits(t) ? t + kRingBytes : t;
+// This file's kernels with dynamic LDS, by walking the dispatch tables above.
+void list_kernels(std::vector<KernelLds> &out) {
+  for (int g = 0; g < 2; g++)
+    for (int c = 0; c < 2; c++)
+      for (int f = 0; f < 2; f++) {
+        list_table(out, kDefR16[g][c][f], "k_mul_vec", [](int k) { return vec_lds(k, 16); });
+        list_table(out, kDefR8[g][c][f], "k_mul_vec", [](int k) { return vec_lds(k, 8); });
+      }
+  list_table(out, kTuneR1, "k_mul_vec tune", [](int k) { return vec_lds(k, 1); });
+  for (const auto &t : kPerm) list_table(out, t, "k_mul_perm", perm_lds);
+  for (KernelFn fn : {&k_mul_vec_dyn<false>, &k_mul_vec_dyn<true>, &k_mul_bytes<false>, &k_mul_bytes<true>})
+    out.push_back({reinterpret_cast<const void *>(fn), "dyn/bytes", bytes_lds(NXEC_MAX_K), false});
+  for (const auto &rows : kScrub)
+    for (const ScrubTable &t : rows) list_table(out, t, "k_scrub_vec", scrub_vec_lds);
+  out.push_back({reinterpret_cast<const void *>(&k_scrub_bytes), "k_scrub_bytes", bytes_lds(NXEC_MAX_K), false});
+  list_table(out, kRagged, "k_mul_ragged", ragged_lds);
 }
 
 }  // namespace
@@ -991,13 +1018,12 @@ LaunchInfo plan_launch(int k, int rows, int64_t vec_count, int64_t nstripes, int
   if (use_perm(k, rows, full, copy, gather)) {
     li.perm = true;
     li.lds_copies = 0;
-    li.lds_bytes = k * 32 + kRingBytes;
+    li.lds_bytes = perm_lds(k);
     li.variant = "vec_perm";
   } else {
     li.lds_copies = choose_r(k, tunable);
-    li.lds_bytes = k * 1024 * li.lds_copies;
-    const bool queued = k <= kMaxTemplK && queue_fits(li.lds_bytes);
-    if (queued) li.lds_bytes += kRingBytes;
+    const bool queued = k <= kMaxTemplK && vec_queued(k, li.lds_copies);
+    li.lds_bytes = k <= kMaxTemplK ? vec_lds(k, li.lds_copies) : bytes_lds(k);
     per_cu = kLdsBytes / (li.lds_bytes > 0 ? li.lds_bytes : 1);
     if (per_cu > 2) per_cu = 2;  // 2 x 16 waves = the CU's 32-wave limit
     if (per_cu < 1) per_cu = 1;
@@ -1014,55 +1040,64 @@ LaunchInfo plan_launch(int k, int rows, int64_t vec_count, int64_t nstripes, int
   return li;
 }
 
-int prepare_kernels() {
-  auto raise = [](KernelFn fn, int lds) -> hipError_t {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  };
-  for (int k = 1; k <= kMaxTemplK; k++) {
-    for (int g = 0; g < 2; g++)
-      for (int c = 0; c < 2; c++)
-        for (int f = 0; f < 2; f++) {
-          if (g && c) continue;
-          for (int r : {16, 8}) {
-            if (r == 16 && k > 10) continue;
-            hipError_t e = raise(vec_kernel(k, r, g, c, f), table_lds(k, r));
-            if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_mul_vec)");
-          }
-        }
-    hipError_t e = raise(kTuneR1[k - 1], table_lds(k, 1));
-    if (e == hipSuccess) e = raise(kDefR8[0][0][1][k - 1], table_lds(k, 8));
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_mul_vec tune)");
-  }
-  for (KernelFn fn : {&k_mul_vec_dyn<false>, &k_mul_vec_dyn<true>, &k_mul_bytes<false>, &k_mul_bytes<true>}) {
-    hipError_t e = raise(fn, NXEC_MAX_K * 1024);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(dyn/bytes)");
-  }
-  for (int r = 0; r < kMaxRowsPerPass; r++)
-    for (int f = 0; f < 2; f++)
-      for (int k = 1; k <= kScrubMaxK; k++) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kScrub[r][f][k - 1]),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, scrub_vec_lds(k));
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_scrub_vec)");
-      }
-  {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_scrub_bytes),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, NXEC_MAX_K * 1024);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_scrub_bytes)");
-  }
-  return prepare_encode_md5();
+void (*mul_kernel(const LaunchInfo &li, int k, bool gather, bool copy, bool full))(MulArgs) {
+  return li.perm ? kPerm[gather][k - 1] : vec_kernel(k, li.lds_copies, gather, copy, full);
 }
+void (*scrub_kernel(int kd, int rows, bool full, int *lds_bytes))(ScrubArgs) {
+  *lds_bytes = scrub_vec_lds(kd);
+  return kScrub[rows - 1][full][kd - 1];
+}
+const void *ragged_kernel(int k, int *lds_bytes) {
+  *lds_bytes = ragged_lds(k);
+  return reinterpret_cast<const void *>(kRagged[k - 1]);
+}
+
+const std::vector<KernelLds> &kernel_lds_list() {
+  static const std::vector<KernelLds> list = [] {
+    std::vector<KernelLds> l;
+    list_kernels(l);
+    list_encode_md5_kernels(l);
+    list_files_md5_kernels(l);
+    return l;
+  }();
+  return list;
+}
+
+int raise_lds(const void *fn, int bytes, const char *family, bool no_static) {
+  hipFuncAttributes fa{};
+  if (no_static && (hipFuncGetAttributes(&fa, fn) != hipSuccess || fa.sharedSizeBytes != 0))
+    return set_error(NXEC_ERR_HIP, "%s: static LDS present (the tables must start at LDS byte 0)", family);
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) return set_error(NXEC_ERR_HIP, "hipFuncSetAttribute(%s): %s", family, hipGetErrorString(e));
+  return NXEC_OK;
+}
+
+int prepare_kernels() {
+  for (const KernelLds &e : kernel_lds_list())
+    if (int rc = raise_lds(e.fn, e.bytes, e.family, e.no_static)) return rc;
+  return NXEC_OK;
+}
+
+namespace {
 
 // Work-queue run length: about 12 tiles' worth of chunk traffic per grab (a
 // 16 KiB tile moves k + rows (+ copies) 16 KiB pieces), so wide stripes grab
 // one tile at a time (the tightest in-flight window) and narrow ones (CAR XOR,
 // small partial encodes) several, which keeps the single counter well under
 // its atomic rate (~80 M/s) and the grab latency hidden.
-uint32_t tiles_per_grab(const MulArgs &a) {
-  int units = a.k + a.rows;
-  if (a.any_copy)
-    for (int j = 0; j < a.k; j++) units += a.copy_off[j] != kNoCopy;
-  const int t = (12 + units - 1) / units;
-  return static_cast<uint32_t>(t < 1 ? 1 : (t > 8 ? 8 : t));
+uint32_t tiles_per_grab(int k, int rows, int copies) {
+  const int units = k + rows + copies;
+  return static_cast<uint32_t>(std::max(1, std::min(8, (12 + units - 1) / units)));
+}
+
+// Chunks of >= 2 MiB at a power-of-two-aligned chunk stride: walk groups of 8
+// stripes column-major, so the in-flight window spans 8 stripes like it does
+// at 1 MiB (4 MiB stride: 0.655 -> 0.711 of 8 TB/s,
+// profiles/r01_chunk_stride_group.log).  A padded stride (the recommended
+// layout, nxec_batch_layout) runs best stripe-major (4 MiB + 2 KiB: 0.758 at
+// sg 1, profiles/r02_layout_sweep.log).
+uint32_t stripe_group_for(int64_t vec_count, bool aliased) {
+  return ((vec_count + kBlock - 1) / kBlock >= 128 && aliased) ? 8 : 1;
 }
 
 // host side of the tile-queue ring: each vector launch draws the next slot
@@ -1088,64 +1123,93 @@ int reset_queue_slots(int first, int count, hipStream_t st) {
   return e == hipSuccess ? NXEC_OK : hip_fail(e, "tile-queue reset");
 }
 
-int launch_failed(hipError_t e, const char *what, int slot, hipStream_t st) {
-  const int rc = hip_fail(e, what);
+int launch_failed(hipError_t e, const char *family, int slot, hipStream_t st) {
+  const int rc = set_error(NXEC_ERR_HIP, "launch %s: %s", family, hipGetErrorString(e));
   if (slot >= 0) (void)reset_queue_slots(slot, 1, st);
   return rc;
 }
 
+// What one launch of a tile-queue kernel (k_mul_vec, k_mul_perm, k_scrub_vec,
+// k_mul_ragged; k_mul_vec_dyn shares k_mul_vec's path) used.  The launch and
+// its record line both read this, so the record cannot drift from the launch.
+struct QueueLaunch {
+  const char *family, *kkey;  // kkey: "k", or "kd" for the scrub
+  int k, rows, r;
+  int gather, copy, full;  // -1: the family has no such form (the key is left out)
+  int pf, q;
+  uint32_t tpg, sg;  // sg 0: no stripe groups (left out)
+  int64_t grid;
+  int lds;
+  int32_t slot;
+};
+
+void record_launch(const QueueLaunch &l) {
+  char s[224];
+  const size_t cap = sizeof s;
+  int n = std::snprintf(s, cap, "family=%s %s=%d rows=%d r=%d", l.family, l.kkey, l.k, l.rows, l.r);
+  if (l.gather >= 0) n += std::snprintf(s + n, cap - n, " gather=%d copy=%d", l.gather, l.copy);
+  if (l.full >= 0) n += std::snprintf(s + n, cap - n, " full=%d", l.full);
+  n += std::snprintf(s + n, cap - n, " pf=%d q=%d tpg=%u", l.pf, l.q, l.tpg);
+  if (l.sg) n += std::snprintf(s + n, cap - n, " sg=%u", l.sg);
+  std::snprintf(s + n, cap - n, " grid=%lld slot=%d", static_cast<long long>(l.grid), l.slot);
+  launch_log_append("%s", s);
+}
+
+// The queue-driven launch: draws the launch's tile-queue slot (draw = false:
+// none, the kernel walks static tile runs) into `slot`, a member of the kernel
+// arguments `a`; records and launches; a failed launch zeroes its slot.
+template <class Args>
+int queue_launch(void (*fn)(Args), const Args &a, int32_t &slot, QueueLaunch &l, hipStream_t st, bool draw = true) {
+  slot = l.slot = draw ? static_cast<int32_t>(g_next_slot.fetch_add(1, std::memory_order_relaxed) % kQueueSlots) : -1;
+  if (launch_log_on()) record_launch(l);
+  hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(l.grid)), dim3(kBlock), l.lds, st, a);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? NXEC_OK : launch_failed(e, l.family, slot, st);
+}
+
+// A chunk's vector range as up to two launches: launch(begin, count, full) for
+// its complete tiles (no lane predicates), then for the ragged remainder.
+template <class F>
+int split_vectors(int64_t vec_count, int64_t nstripes, const F &launch) {
+  const int64_t tps = (vec_count + kBlock - 1) / kBlock;
+  if (tps * nstripes >= (int64_t(1) << 32) || vec_count >= (int64_t(1) << 32))
+    return set_error(NXEC_ERR_INVALID, "batch too large for one launch (split nstripes)");
+  const int64_t full = vec_count / kBlock * kBlock;
+  int rc = full > 0 ? launch(int64_t(0), full, true) : NXEC_OK;
+  if (rc == NXEC_OK && vec_count > full) rc = launch(full, vec_count - full, false);
+  return rc;
+}
+
+}  // namespace
 
 int launch_mul(const MulArgs &a, bool vec_ok, int num_cus, void *stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (a.nstripes <= 0 || a.len <= 0) return NXEC_OK;
   if (vec_ok && a.vec_count > 0) {
-    const int64_t tps = (a.vec_count + kBlock - 1) / kBlock;
-    if (tps * a.nstripes >= (int64_t(1) << 32) || a.vec_count >= (int64_t(1) << 32))
-      return set_error(NXEC_ERR_INVALID, "batch too large for one launch (split nstripes)");
-    const bool gather = a.src_ptrs != nullptr;
-    const bool copy = a.any_copy != 0;
-    // complete tiles first (no lane predicates), then the ragged remainder
-    const int64_t full = a.vec_count / kBlock * kBlock;
-    const int64_t parts[2][2] = {{0, full}, {full, a.vec_count - full}};
-    for (int pi = 0; pi < 2; pi++) {
-      if (parts[pi][1] <= 0) continue;
+    const bool gather = a.src_ptrs != nullptr, copy = a.any_copy != 0;
+    const bool dyn = a.k > kMaxTemplK;  // static tile runs: no queue, no stripe groups
+    int copies = 0;
+    for (int j = 0; copy && j < a.k; j++) copies += a.copy_off[j] != kNoCopy;
+    const uint32_t tpg = tiles_per_grab(a.k, a.rows, copies);
+    const bool aliased = gather || a.src_chunk_stride % (int64_t(1) << 20) == 0;
+    const uint32_t sg = tuning().stripe_group > 0 ? static_cast<uint32_t>(tuning().stripe_group)
+                                                  : stripe_group_for(a.vec_count, aliased);
+    const int rc = split_vectors(a.vec_count, a.nstripes, [&](int64_t begin, int64_t count, bool full) {
       MulArgs b = a;
-      b.queue_slot = tuning().static_order ? -1 : static_cast<int32_t>(g_next_slot.fetch_add(1, std::memory_order_relaxed) % kQueueSlots);
-      b.tiles_per_grab = tiles_per_grab(b);
-      // chunks of >= 2 MiB at a power-of-two-aligned chunk stride: walk groups
-      // of 8 stripes column-major, so the in-flight window spans 8 stripes
-      // like it does at 1 MiB (4 MiB stride: 0.655 -> 0.711 of 8 TB/s,
-      // profiles/r01_chunk_stride_group.log).  A padded stride (the
-      // recommended layout, nxec_batch_layout) runs best stripe-major
-      // (4 MiB + 2 KiB: 0.758 at sg 1, profiles/r02_layout_sweep.log).
-      const bool aliased = a.src_ptrs != nullptr || a.src_chunk_stride % (int64_t(1) << 20) == 0;
-      b.stripe_group = ((b.vec_count + kBlock - 1) / kBlock >= 128 && aliased) ? 8 : 1;
-      if (tuning().stripe_group > 0) b.stripe_group = static_cast<uint32_t>(tuning().stripe_group);
-      b.vec_begin = a.vec_begin + parts[pi][0];
-      b.vec_count = parts[pi][1];
-      const bool is_full = pi == 0;
-      LaunchInfo li = plan_launch(b.k, b.rows, b.vec_count, b.nstripes, num_cus, is_full, copy, gather);
-      KernelFn fn = li.perm ? kPerm[gather][b.k - 1] : vec_kernel(b.k, li.lds_copies, gather, copy, is_full);
-      if (launch_log_on()) {
-        if (li.perm)
-          launch_log_append("family=k_mul_perm k=%d rows=%d r=0 gather=%d copy=0 full=1 pf=%d q=1 tpg=%u sg=%u "
-                            "grid=%d slot=%d",
-                            b.k, b.rows, gather, perm_prefetch(b.k), b.tiles_per_grab, b.stripe_group, li.grid,
-                            b.queue_slot);
-        else if (b.k > kMaxTemplK)
-          launch_log_append("family=k_mul_vec_dyn k=%d rows=%d r=1 gather=%d copy=%d full=%d pf=0 q=0 tpg=0 sg=1 "
-                            "grid=%d slot=-1",
-                            b.k, b.rows, gather, copy, is_full, li.grid);
-        else
-          launch_log_append("family=k_mul_vec k=%d rows=%d r=%d gather=%d copy=%d full=%d pf=%d q=%d tpg=%u sg=%u "
-                            "grid=%d slot=%d",
-                            b.k, b.rows, li.lds_copies, gather, copy, is_full, vec_prefetch(b.k, copy, is_full),
-                            vec_queued(b.k, li.lds_copies), b.tiles_per_grab, b.stripe_group, li.grid, b.queue_slot);
-      }
-      hipLaunchKernelGGL(fn, dim3(li.grid), dim3(li.block), li.lds_bytes, st, b);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return launch_failed(e, "launch k_mul_vec", b.queue_slot, st);
-    }
+      b.tiles_per_grab = tpg;
+      b.stripe_group = sg;
+      b.vec_begin = a.vec_begin + begin;
+      b.vec_count = count;
+      const LaunchInfo li = plan_launch(b.k, b.rows, count, b.nstripes, num_cus, full, copy, gather);
+      QueueLaunch l{li.perm ? "k_mul_perm" : dyn ? "k_mul_vec_dyn" : "k_mul_vec", "k", b.k, b.rows,
+                    li.lds_copies, gather, copy, full,
+                    li.perm ? perm_prefetch(b.k) : !dyn && vec_prefetch(b.k, copy, full),
+                    li.perm || (!dyn && vec_queued(b.k, li.lds_copies)), dyn ? 0 : tpg, dyn ? 1 : sg, li.grid,
+                    li.lds_bytes, 0};
+      return queue_launch(mul_kernel(li, b.k, gather, copy, full), b, b.queue_slot, l, st,
+                          !dyn && !tuning().static_order);
+    });
+    if (rc) return rc;
   }
   if (a.byte_begin < a.len) {
     const int64_t total = (a.len - a.byte_begin) * a.nstripes;
@@ -1157,7 +1221,7 @@ int launch_mul(const MulArgs &a, bool vec_ok, int num_cus, void *stream) {
                         "byte_begin=%lld",
                         a.k, a.rows, a.src_ptrs != nullptr, a.any_copy != 0, static_cast<long long>(blocks),
                         static_cast<long long>(a.byte_begin));
-    hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(blocks)), dim3(256), a.k * 1024, st, a);
+    hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(blocks)), dim3(256), bytes_lds(a.k), st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch k_mul_bytes");
   }
@@ -1178,34 +1242,24 @@ int launch_scrub_detect(const ScrubArgs &a0, bool vec_ok, int num_cus, void *str
   m.vec_count = vec ? m.len / 16 : 0;
   m.byte_begin = m.vec_count * 16;
   if (m.vec_count > 0) {
-    const int64_t tps = (m.vec_count + kBlock - 1) / kBlock;
-    if (tps * m.nstripes >= (int64_t(1) << 32) || m.vec_count >= (int64_t(1) << 32))
-      return set_error(NXEC_ERR_INVALID, "batch too large for one launch (split nstripes)");
     for (int r = 0; r < m.rows; r++) m.src_off[m.k + r] = a.par_off[r];
-    // complete tiles first (no lane predicates), then the ragged remainder
-    const int64_t full = m.vec_count / kBlock * kBlock;
-    const int64_t parts[2][2] = {{0, full}, {full, m.vec_count - full}};
-    for (int pi = 0; pi < 2; pi++) {
-      if (parts[pi][1] <= 0) continue;
+    // The encode's run length and tile order (launch_mul), always queue-driven
+    // and never with its two tuning knobs: tuning().static_order and
+    // tuning().stripe_group are A/B probes of the encode kernels, and a scrub
+    // that changed with them would only blur those measurements.
+    m.tiles_per_grab = tiles_per_grab(m.k, m.rows, 0);
+    m.stripe_group = stripe_group_for(m.vec_count, m.src_chunk_stride % (int64_t(1) << 20) == 0);
+    const int rc = split_vectors(m.vec_count, m.nstripes, [&](int64_t begin, int64_t count, bool full) {
       ScrubArgs b = a;
-      b.m.queue_slot = static_cast<int32_t>(g_next_slot.fetch_add(1, std::memory_order_relaxed) % kQueueSlots);
-      b.m.tiles_per_grab = tiles_per_grab(b.m);
-      // the encode's tile order (launch_mul): groups of 8 stripes for big chunks at an aliasing stride
-      const bool aliased = m.src_chunk_stride % (int64_t(1) << 20) == 0;
-      b.m.stripe_group = ((m.vec_count + kBlock - 1) / kBlock >= 128 && aliased) ? 8 : 1;
-      b.m.vec_begin = parts[pi][0];
-      b.m.vec_count = parts[pi][1];
-      const int64_t ntiles = (b.m.vec_count + kBlock - 1) / kBlock * b.m.nstripes;
-      const int64_t grid = std::min<int64_t>(num_cus, ntiles);
-      if (launch_log_on())
-        launch_log_append("family=k_scrub_vec kd=%d rows=%d r=%d full=%d pf=%d q=1 tpg=%u sg=%u grid=%lld slot=%d", m.k,
-                          m.rows, default_r(m.k), pi == 0, scrub_prefetch(m.k + m.rows, pi == 0), b.m.tiles_per_grab,
-                          b.m.stripe_group, static_cast<long long>(grid), b.m.queue_slot);
-      hipLaunchKernelGGL(kScrub[m.rows - 1][pi == 0][m.k - 1], dim3(static_cast<unsigned>(grid)), dim3(kBlock),
-                         scrub_vec_lds(m.k), st, b);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return launch_failed(e, "launch k_scrub_vec", b.m.queue_slot, st);
-    }
+      b.m.vec_begin = begin;
+      b.m.vec_count = count;
+      const int64_t ntiles = (count + kBlock - 1) / kBlock * m.nstripes;
+      QueueLaunch l{"k_scrub_vec", "kd", m.k, m.rows, default_r(m.k), -1, -1, full,
+                    scrub_prefetch(m.k + m.rows, full), 1, m.tiles_per_grab, m.stripe_group,
+                    std::min<int64_t>(num_cus, ntiles), 0, 0};
+      return queue_launch(scrub_kernel(m.k, m.rows, full, &l.lds), b, b.m.queue_slot, l, st);
+    });
+    if (rc) return rc;
   }
   if (m.byte_begin < m.len) {
     const int64_t total = (m.len - m.byte_begin) * m.nstripes;
@@ -1214,7 +1268,7 @@ int launch_scrub_detect(const ScrubArgs &a0, bool vec_ok, int num_cus, void *str
     if (launch_log_on())
       launch_log_append("family=k_scrub_bytes kd=%d rows=%d grid=%lld byte_begin=%lld", m.k, m.rows,
                         static_cast<long long>(blocks), static_cast<long long>(m.byte_begin));
-    hipLaunchKernelGGL(k_scrub_bytes, dim3(static_cast<unsigned>(blocks)), dim3(256), m.k * 1024, st, a);
+    hipLaunchKernelGGL(k_scrub_bytes, dim3(static_cast<unsigned>(blocks)), dim3(256), bytes_lds(m.k), st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch k_scrub_bytes");
   }
@@ -1269,7 +1323,7 @@ int launch_mul_list(int rows, int k, const uint8_t *coeffs, const ListStripe *d_
       for (int j = 0; j < k; j++) a.coef[r * k + j] = coeffs[static_cast<size_t>(r0 + r) * k + j];
     if (launch_log_on())
       launch_log_append("family=k_mul_list k=%d rows=%d grid=%lld", k, a.rows, static_cast<long long>(blocks));
-    hipLaunchKernelGGL(k_mul_list, dim3(static_cast<unsigned>(blocks)), dim3(256), k * 1024,
+    hipLaunchKernelGGL(k_mul_list, dim3(static_cast<unsigned>(blocks)), dim3(256), bytes_lds(k),
                        static_cast<hipStream_t>(stream), a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch k_mul_list");
@@ -1277,27 +1331,11 @@ int launch_mul_list(int rows, int k, const uint8_t *coeffs, const ListStripe *d_
   return NXEC_OK;
 }
 
-using RaggedFn = void (*)(RaggedArgs);
-template <int... Ks>
-constexpr std::array<RaggedFn, sizeof...(Ks)> ragged_table(std::integer_sequence<int, Ks...>) {
-  return {{&k_mul_ragged<Ks + 1, default_r(Ks + 1)>...}};
-}
-const std::array<RaggedFn, kMaxRaggedK> kRagged = ragged_table(std::make_integer_sequence<int, kMaxRaggedK>{});
-int ragged_lds(int k) { return k * 1024 * default_r(k) + kRingBytes; }
-
 int launch_mul_ragged(int rows, int k, const uint8_t *coeffs, const ListStripe *d_stripes, const uint32_t *d_tile_stripe,
                       const uint32_t *d_stripe_tile0, int64_t ntiles, int num_cus, void *stream) {
   if (ntiles <= 0 || rows <= 0) return NXEC_OK;
   if (k < 1 || k > kMaxRaggedK) return set_error(NXEC_ERR_INVALID, "ragged launch: k=%d unsupported", k);
   if (ntiles >= (int64_t(1) << 32)) return set_error(NXEC_ERR_INVALID, "ragged launch: too many tiles");
-  static const bool raised = [] {
-    for (int kk = 1; kk <= kMaxRaggedK; kk++)
-      if (hipFuncSetAttribute(reinterpret_cast<const void *>(kRagged[kk - 1]),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, ragged_lds(kk)) != hipSuccess)
-        return false;
-    return true;
-  }();
-  if (!raised) return set_error(NXEC_ERR_HIP, "hipFuncSetAttribute(k_mul_ragged) failed");
   const int64_t grid = std::min<int64_t>(num_cus, ntiles);
   for (int r0 = 0; r0 < rows; r0 += kMaxRowsPerPass) {
     RaggedArgs a;
@@ -1309,17 +1347,12 @@ int launch_mul_ragged(int rows, int k, const uint8_t *coeffs, const ListStripe *
     a.k = k;
     a.rows = rows - r0 < kMaxRowsPerPass ? rows - r0 : kMaxRowsPerPass;
     a.row0 = r0;
-    a.queue_slot = static_cast<int32_t>(g_next_slot.fetch_add(1, std::memory_order_relaxed) % kQueueSlots);
-    a.tiles_per_grab = std::max(1, std::min(8, (12 + k + a.rows - 1) / (k + a.rows)));
+    a.tiles_per_grab = tiles_per_grab(k, a.rows, 0);
     for (int r = 0; r < a.rows; r++)
       for (int j = 0; j < k; j++) a.coef[r * k + j] = coeffs[static_cast<size_t>(r0 + r) * k + j];
-    if (launch_log_on())
-      launch_log_append("family=k_mul_ragged k=%d rows=%d r=%d pf=%d q=1 tpg=%u grid=%lld slot=%d", k, a.rows,
-                        default_r(k), ragged_prefetch(k), a.tiles_per_grab, static_cast<long long>(grid), a.queue_slot);
-    hipLaunchKernelGGL(kRagged[k - 1], dim3(static_cast<unsigned>(grid)), dim3(kBlock), ragged_lds(k),
-                       static_cast<hipStream_t>(stream), a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return launch_failed(e, "launch k_mul_ragged", a.queue_slot, static_cast<hipStream_t>(stream));
+    QueueLaunch l{"k_mul_ragged", "k", k, a.rows, default_r(k), -1, -1, -1, ragged_prefetch(k), 1,
+                  a.tiles_per_grab, 0, grid, ragged_lds(k), 0};
+    if (int rc = queue_launch(kRagged[k - 1], a, a.queue_slot, l, static_cast<hipStream_t>(stream))) return rc;
   }
   return NXEC_OK;
 }
@@ -1332,15 +1365,6 @@ int launch_pad_chunks(const PadChunks *d_items, const uint32_t *d_bstart, int64_
                      d_items, d_bstart, nitems);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? NXEC_OK : hip_fail(e, "launch k_pad_chunks");
-}
-
-int launch_pad_copy(const PadCopy *d_items, int64_t nitems, void *stream) {
-  if (nitems <= 0) return NXEC_OK;
-  if (nitems * kPadParts >= (int64_t(1) << 31)) return set_error(NXEC_ERR_INVALID, "too many pad-copy items");
-  hipLaunchKernelGGL(k_pad_copy, dim3(static_cast<unsigned>(nitems * kPadParts)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), d_items);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NXEC_OK : hip_fail(e, "launch k_pad_copy");
 }
 
 int launch_copy16(void *dst, const void *src, size_t bytes, int num_cus, void *stream) {

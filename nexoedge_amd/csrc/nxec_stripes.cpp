@@ -80,9 +80,7 @@ int stripes_mul_impl(nxec_ctx_t *ctx, int rows, int k, const unsigned char *coef
   a.vec_count = vec_count;
   a.byte_begin = vec_count * 16;
 
-  // split nstripes so one launch's tile count fits 32 bits
-  const int64_t tps = std::max<int64_t>(1, (vec_count + 1023) / 1024);
-  const int64_t max_stripes = std::max<int64_t>(1, ((int64_t(1) << 31) / tps));
+  const int64_t max_stripes = max_stripes_per_launch(vec_count);
 
   const int passes = rows == 0 ? 1 : (rows + kMaxRowsPerPass - 1) / kMaxRowsPerPass;
   for (int p = 0; p < passes; p++) {
@@ -246,9 +244,7 @@ int nxec_rs_scrub_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripe
     a.m.copy_off[j] = kNoCopy;
   }
   const bool vec_ok = aligned16(d_stripes) && chunk_stride % 16 == 0 && stripe_stride % 16 == 0;
-  // split nstripes so one launch's tile count fits 32 bits
-  const int64_t tps = std::max<int64_t>(1, (len / 16 + 1023) / 1024);
-  const int64_t max_stripes = std::max<int64_t>(1, ((int64_t(1) << 31) / tps));
+  const int64_t max_stripes = max_stripes_per_launch(len / 16);
   // detect: one pass per 4 parity rows, every pass flagging the same status word
   for (int r0 = 0; r0 < m; r0 += kMaxRowsPerPass) {
     const int pr = std::min(kMaxRowsPerPass, m - r0);

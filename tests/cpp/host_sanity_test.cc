@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <atomic>
 #include <functional>
+#include <map>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -393,9 +394,56 @@ static void launch_record(int t) {
   }
 }
 
+// The per-device preparation list (nxec::kernel_lds_list) against the dispatch
+// over its whole domain: every kernel a launch can pick is listed, with at
+// least the dynamic LDS that launch asks for and no more than the CU has.
+// Taking a kernel's address needs no device.
+static void kernel_lds_registry() {
+  std::map<const void *, int> listed;
+  for (const nxec::KernelLds &e : nxec::kernel_lds_list()) {
+    CHECK(e.fn && e.family && e.bytes > 0 && e.bytes <= 160 * 1024, "entry %s: %d bytes", e.family ? e.family : "?", e.bytes);
+    const auto ins = listed.emplace(e.fn, e.bytes);
+    CHECK(ins.second || ins.first->second == e.bytes, "%s listed with %d and %d bytes", e.family, ins.first->second, e.bytes);
+  }
+  int points = 0;
+  auto covered = [&](const void *fn, int lds, const char *what, int k, int rows, int form, int full) {
+    points++;
+    CHECK(fn != nullptr, "%s k=%d rows=%d form=%d full=%d: no kernel", what, k, rows, form, full);
+    const auto it = listed.find(fn);
+    CHECK(it != listed.end(), "%s k=%d rows=%d form=%d full=%d: not in the preparation list", what, k, rows, form, full);
+    if (it != listed.end())
+      CHECK(it->second >= lds && lds > 0, "%s k=%d rows=%d form=%d full=%d: launch asks %d bytes, %d prepared", what, k,
+            rows, form, full, lds, it->second);
+  };
+  for (int k = 1; k <= 24; k++)
+    for (int rows = 1; rows <= 4; rows++)
+      for (int form = 0; form < 3; form++)  // strided, copy, gather (no gather form carries copies)
+        for (int full = 0; full < 2; full++) {
+          const bool copy = form == 1, gather = form == 2;
+          const nxec::LaunchInfo li = nxec::plan_launch(k, rows, 1024, 1, 256, full, copy, gather);
+          covered(reinterpret_cast<const void *>(nxec::mul_kernel(li, k, gather, copy, full)), li.lds_bytes, "mul", k, rows,
+                  form, full);
+        }
+  for (int kd = 1; kd <= nxec::kScrubMaxK; kd++)
+    for (int rows = 1; rows <= 4; rows++)
+      for (int full = 0; full < 2; full++) {
+        CHECK(nxec::scrub_vec_shape(kd, rows), "scrub shape kd=%d rows=%d", kd, rows);
+        int lds = 0;
+        const void *fn = reinterpret_cast<const void *>(nxec::scrub_kernel(kd, rows, full, &lds));
+        covered(fn, lds, "scrub", kd, rows, 0, full);
+      }
+  for (int k = 1; k <= nxec::kMaxRaggedK; k++) {
+    int lds = 0;
+    const void *fn = nxec::ragged_kernel(k, &lds);
+    covered(fn, lds, "ragged", k, 0, 0, 0);
+  }
+  std::printf("kernel LDS registry: %zu kernels listed, %d dispatch points checked\n", listed.size(), points);
+}
+
 int main() {
   gf_and_planning();
   files_slot_plan();
+  kernel_lds_registry();
   argument_validation();
   ini_files();
   std::vector<std::thread> th;
