@@ -15,7 +15,7 @@ OBJDIR   := build/obj
 
 LIB_SRCS := $(CSRC)/gf_host.cpp $(CSRC)/nxec_context.cpp $(CSRC)/nxec_stripes.cpp $(CSRC)/nxec_objects.cpp \
             $(CSRC)/nxec_host_paths.cpp $(CSRC)/nxec_host_encode.cpp $(CSRC)/nxec_agent.cpp $(CSRC)/nxec_probes.cpp \
-            $(CSRC)/nxec_scrub_host.cpp \
+            $(CSRC)/nxec_scrub_host.cpp $(CSRC)/nxec_recover_mixed_host.cpp \
             $(CSRC)/nxec_kernels.hip $(CSRC)/nxec_md5.hip $(CSRC)/nxec_encode_md5.hip $(CSRC)/nxec_encode_md5_ring.hip \
             $(CSRC)/nxec_files_md5.hip \
             $(CSRC)/nxec_group.cpp $(CSRC)/nxec_host_arena.cpp $(CSRC)/nxec_digest.cpp $(CSRC)/nxec_digest_place.cpp $(CSRC)/nxec_numa.cpp $(CSRC)/nxec_config.cpp \
@@ -24,7 +24,8 @@ LIB_OBJS := $(patsubst $(CSRC)/%,$(OBJDIR)/%.o,$(LIB_SRCS))
 HDRS     := include/nxec.h $(CSRC)/nxec_internal.h $(CSRC)/nxec_runtime.h $(CSRC)/nxec_tuning.h $(CSRC)/nxec_device.h $(CSRC)/nxec_em_common.h $(CSRC)/nxec_scrub_rule.h $(wildcard $(CSRC)/coding/*.hh)
 
 all: $(LIBDIR)/libnxec.so oracle/liboracle.so build/rs_surface_test build/isal_compat_test build/chunk_manager_flow_test \
-     build/stripe_batch_test build/chunk_replay_test build/dropin_pool_test build/scrub_host_test
+     build/stripe_batch_test build/chunk_replay_test build/dropin_pool_test build/scrub_host_test \
+     build/recover_mixed_plan_test build/recover_mixed_registry_test
 
 # rs.cc's ISA-L call sequence compiled against include/nxec_isal_compat.h (plain C)
 build/isal_compat_test: tests/cpp/isal_compat_test.c include/nxec_isal_compat.h $(LIBDIR)/libnxec.so
@@ -71,6 +72,22 @@ build/scrub_host_test: tests/cpp/scrub_host_test.cc $(CSRC)/nxec_scrub_host.cpp 
 	    -Iinclude -I$(CSRC) tests/cpp/scrub_host_test.cc $(CSRC)/nxec_scrub_host.cpp $(CSRC)/gf_host.cpp -o $@
 scrub-host-test: build/scrub_host_test
 	build/scrub_host_test
+
+# the mixed-pattern recover's host planner (nxec_rs_recover_mixed_plan) the same way: ASan + UBSan,
+# the planner source and gf_host.cpp, no device and no libnxec
+build/recover_mixed_plan_test: tests/cpp/recover_mixed_plan_test.cc $(CSRC)/nxec_recover_mixed_host.cpp $(CSRC)/gf_host.cpp $(HDRS)
+	@mkdir -p build
+	g++ -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
+	    -Iinclude -I$(CSRC) tests/cpp/recover_mixed_plan_test.cc $(CSRC)/nxec_recover_mixed_host.cpp $(CSRC)/gf_host.cpp -o $@
+recover-mixed-plan-test: build/recover_mixed_plan_test
+	build/recover_mixed_plan_test
+
+# the kernel the mixed launch picks for every k against the per-device preparation list (no sanitizers, no device)
+build/recover_mixed_registry_test: tests/cpp/recover_mixed_registry_test.cc $(LIBDIR)/libnxec.so $(HDRS)
+	@mkdir -p build
+	g++ -std=c++17 -O2 -Wall -Iinclude -I$(CSRC) $< -L$(LIBDIR) -lnxec -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -lcrypto -o $@
+recover-mixed-registry-test: build/recover_mixed_registry_test
+	build/recover_mixed_registry_test
 
 $(OBJDIR)/%.o: $(CSRC)/% $(HDRS)
 	@mkdir -p $(dir $@)
@@ -147,4 +164,5 @@ golden: ref
 clean:
 	rm -rf build $(LIBDIR)/libnxec.so oracle/liboracle.so
 
-.PHONY: all ref golden clean tune tools asan ubsan tsan sanitize scrub-host-test
+.PHONY: all ref golden clean tune tools asan ubsan tsan sanitize scrub-host-test recover-mixed-plan-test \
+        recover-mixed-registry-test

@@ -225,6 +225,58 @@ int nxec_rs_recover_stripes(nxec_ctx_t *ctx, int n, int k, const int32_t *failed
                             unsigned char *d_stripes, int64_t chunk_stride, int64_t stripe_stride, int64_t len,
                             int64_t nstripes, void *stream);
 
+/* Mixed-pattern recover: the same repair for a batch whose stripes lost
+ * different chunks, as the detectors report it.  alive (HOST, [nstripes][n])
+ * has the layout of d_ok of nxec_md5_verify_chunks / nxec_decode_object_verify,
+ * so a downloaded ok map is a valid alive map: byte (s, c) != 0 means chunk c
+ * of stripe s is present and trusted, 0 that it is erased.  Per stripe, with E
+ * the ascending erased ids:
+ *   |E| == 0          not touched, result 0;
+ *   |E| > n-k         not touched, result NXEC_RECOVER_LOST;
+ *   nxec_rs_plan(n, k, E, |E|, 1, ...) is singular
+ *                     not touched, result NXEC_RECOVER_SINGULAR;
+ *   otherwise         the chunks in E are rebuilt in place from the first k
+ *                     alive chunks, result |E|: byte for byte what
+ *                     nxec_rs_recover_stripes(ctx, n, k, E, |E|, ...) does to
+ *                     that stripe alone (the same plan, rs.cc:238-322).
+ * "Not touched": no byte of the stripe is read or written.  Erased slots are
+ * only written; bytes between chunks (stride padding) are never written.
+ *
+ * alive is read and result (HOST, [nstripes], may be NULL) written before the
+ * call returns; both may be reused at once.  The device work is asynchronous
+ * on `stream` with no host synchronisation inside: the device tables are
+ * staged in a context slot released with an event, as
+ * nxec_encode_objects_ex(NXEC_OBJECTS_ASYNC) stages its tables.
+ *
+ * Two paths, shown by the launch record (nxec_debug_launch_log):
+ *   one launch  k <= 19, d_stripes, chunk_stride and stripe_stride 16-byte
+ *               aligned and len % 16 == 0: the distinct patterns are planned
+ *               once each, and one queue-driven kernel (k_mul_mixed) walks
+ *               every coded stripe, rebuilding its LDS tables where the
+ *               pattern changes (a pattern of more than 4 erased chunks runs
+ *               as ceil(|E|/4) segments over the same sources);
+ *   by runs     every other shape (k > 19, unaligned layouts, sub-16-byte
+ *               tails): one nxec_rs_recover_stripes per maximal run of
+ *               consecutive stripes with equal pattern.  Correct for every
+ *               shape the library accepts.
+ *
+ * NULL ctx, invalid (n,k), NULL alive with nstripes > 0, negative len or
+ * nstripes, NULL d_stripes when there is work to do, or chunk offsets of a
+ * stripe beyond 4 GiB give NXEC_ERR_INVALID before any device use (result is
+ * then not written).  len == 0, nstripes == 0 or n == k launch nothing;
+ * result is still filled. */
+#define NXEC_RECOVER_LOST (-1)     /* more than n-k chunks of the stripe are erased */
+#define NXEC_RECOVER_SINGULAR (-2) /* its first k alive chunks do not invert (nxec_rs_plan's NXEC_ERR_SINGULAR) */
+int nxec_rs_recover_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned char *alive,
+                                  unsigned char *d_stripes, int64_t chunk_stride, int64_t stripe_stride, int64_t len,
+                                  int64_t nstripes, int32_t *result, void *stream);
+/* The host half alone (pure, no device): result as above (may be NULL);
+ * *npatterns = distinct decodable patterns with |E| >= 1, *nsegments = the sum
+ * over those patterns of ceil(|E| / 4), *ncoded = stripes with result > 0
+ * (each may be NULL). */
+int nxec_rs_recover_mixed_plan(int n, int k, const unsigned char *alive, int64_t nstripes, int32_t *result,
+                               int64_t *npatterns, int64_t *nsegments, int64_t *ncoded);
+
 /* Parity scrub: are the n chunks of every stripe still a codeword, and if
  * not, which chunk is wrong?  Needs no stored digests, and sees a torn stripe
  * (data rewritten, parity not) that nxec_md5_verify_chunks cannot.

@@ -60,6 +60,9 @@ _PROTOS = {
     "nxec_stripes_mul_ptrs": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, i64, i64, vp]),
     "nxec_rs_encode_stripes": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, i64, i64, i64, vp]),
     "nxec_rs_recover_stripes": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, i64, i64, i64, i64, vp]),
+    "nxec_rs_recover_stripes_mixed": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, i64, i64, i64, i64, vp, vp]),
+    "nxec_rs_recover_mixed_plan": (C.c_int, [C.c_int, C.c_int, vp, i64, vp, C.POINTER(i64), C.POINTER(i64),
+                                             C.POINTER(i64)]),
     "nxec_rs_scrub_stripes": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, i64, i64, i64, C.c_int, vp, vp, vp]),
     "nxec_rs_syndrome_locate": (C.c_int, [C.c_int, C.c_int, vp, i32p, u8p]),
     "nxec_rs_decode_stripes": (
@@ -200,6 +203,9 @@ NXEC_SCRUB_CLEAN = -1
 NXEC_SCRUB_UNLOCATED = -2
 NXEC_SCRUB_LOCATE = 1
 NXEC_SCRUB_REPAIR = 2
+
+NXEC_RECOVER_LOST = -1
+NXEC_RECOVER_SINGULAR = -2
 
 
 class NxecError(RuntimeError):

@@ -202,6 +202,48 @@ constexpr int kMaxRaggedK = 19;
 const void *ragged_kernel(int k, int *lds_bytes);
 int launch_mul_ragged(int rows, int k, const uint8_t *coeffs, const ListStripe *d_stripes, const uint32_t *d_tile_stripe,
                       const uint32_t *d_stripe_tile0, int64_t ntiles, int num_cus, void *stream);
+// Mixed-pattern recover (nxec_rs_recover_stripes_mixed): every stripe of the
+// batch names its own erased chunks.  Host half (nxec_recover_mixed_host.cpp,
+// pure arithmetic, no device): the distinct patterns, one nxec_rs_plan each.
+struct MixedPlan {
+  struct Pattern {
+    std::vector<int32_t> erased;  // ascending ids, 1 .. n-k of them
+    std::vector<int32_t> inputs;  // the first k alive ids
+    std::vector<uint8_t> rows;    // |erased| x k repair matrix (nxec_rs_plan)
+  };
+  std::vector<Pattern> patterns;    // decodable patterns, in order of first appearance
+  std::vector<int32_t> pattern_of;  // per stripe: index into patterns, -1 when nothing is coded
+  int64_t nsegments = 0;            // sum over the patterns of ceil(|erased| / kMaxRowsPerPass)
+  int64_t ncoded = 0;               // stripes with result > 0
+};
+// result[s] (nstripes entries, may be NULL) as nxec_rs_recover_stripes_mixed
+// documents it; arguments are validated by the caller.
+void mixed_plan(int n, int k, const uint8_t *alive, int64_t nstripes, int32_t *result, MixedPlan *plan);
+// One segment of a pattern as the kernel reads it: <= 4 repair rows over the
+// pattern's k sources, 32-bit byte offsets inside a stripe like MulArgs.
+// Coefficient rows >= rows are zero.
+struct MixedSeg {
+  uint32_t rows;
+  uint32_t dst_off[kMaxRowsPerPass];
+  uint32_t src_off[kMaxRaggedK];
+  uint8_t coef[kMaxRowsPerPass * kMaxRaggedK];  // row-major rows x k
+  uint8_t pad[4];
+};
+static_assert(sizeof(MixedSeg) % 16 == 0, "segment records are staged 16-byte aligned");
+// The device tables of a plan (k <= kMaxRaggedK, chunk offsets below 4 GiB):
+// the segment records; order[i], the stripe of the i-th coded item (items run
+// by segment, then ascending stripe; a stripe with more than 4 erased chunks
+// appears once per segment of its pattern); seg_of[i], its segment.
+void mixed_tables(const MixedPlan &plan, int k, int64_t chunk_stride, std::vector<MixedSeg> &segs,
+                  std::vector<uint32_t> &order, std::vector<uint32_t> &seg_of);
+// The mixed kernel of k <= kMaxRaggedK and the dynamic LDS its launch asks for.
+const void *mixed_kernel(int k, int *lds_bytes);
+// One launch over nitems coded items of len bytes per chunk (a multiple of 16;
+// base, strides and offsets 16-byte aligned); tables in device memory.
+// nsegs / ncoded only go to the launch record.
+int launch_mul_mixed(int k, uint8_t *base, int64_t stripe_stride, int64_t len, const MixedSeg *d_segs,
+                     const uint32_t *d_order, const uint32_t *d_seg_of, int64_t nitems, int64_t nsegs, int64_t ncoded,
+                     int num_cus, void *stream);
 // Last stripe of an object into the aligned tail arena: dst + j*cls (j < k)
 // receives object bytes [j*cl, (j+1)*cl) of src (zeros past rem) then zeros
 // up to cls (a multiple of 16 >= cl).  Item i owns 256-thread blocks

@@ -556,6 +556,97 @@ __global__ __launch_bounds__(kBlock) void k_mul_ragged(const RaggedArgs a) {
   tile_loop<K, PF, true, true>(load, run, a.ntiles, a.queue_slot, a.tiles_per_grab, tab + kLds / 4);
 }
 
+// --- mixed-pattern recover (nxec_rs_recover_stripes_mixed) ---
+// Every coded stripe names its own erased chunks.  Item i = stripe order[i]
+// under segment seg_of[i] (one pattern's <= 4 repair rows over its k sources);
+// tile t = column tile t % tps of item t / tps.  Items run by segment, so a
+// workgroup's tables stay valid for long stretches; where the segment of the
+// tile it is about to run differs from the resident one it rebuilds them from
+// the segment record.  The tile index is workgroup-uniform (tile_loop), so the
+// rebuild and its two barriers are too.  Item, stripe and segment stay in
+// SGPRs (scalar loads of uniform addresses); only the vector index is per lane.
+struct MixedArgs {
+  uint8_t *base;
+  int64_t stripe_stride;
+  const MixedSeg *__restrict__ segs;
+  const uint32_t *__restrict__ order;
+  const uint32_t *__restrict__ seg_of;
+  uint32_t ntiles, tps, nvec;
+  int32_t queue_slot;
+  uint32_t tiles_per_grab;
+};
+
+constexpr int mixed_lds(int k) { return vec_lds(k, default_r(k)); }
+
+// The launch's tables are written by the host before it starts and by no
+// kernel: read through the constant address space, a load at a uniform index
+// is a scalar load and its result stays in SGPRs (a global load would not be,
+// next to the kernel's own stores).
+template <class T>
+__device__ __forceinline__ const __attribute__((address_space(4))) T *const_table(const T *p) {
+  return (const __attribute__((address_space(4))) T *)(reinterpret_cast<uintptr_t>(p));
+}
+
+template <int K, int R>
+__global__ __launch_bounds__(kBlock) void k_mul_mixed(const MixedArgs a) {
+  constexpr bool PF = ragged_prefetch(K);
+  constexpr int kLds = table_bytes(K, R);
+  static_assert(R == default_r(K) && kLds + kRingBytes == mixed_lds(K), "mixed kernels are queue-driven");
+  extern __shared__ uint32_t tab[];
+  const char *tl = reinterpret_cast<const char *>(tab) + (threadIdx.x % R) * 4;
+  uint32_t resident = ~0u;  // the segment whose tables are in LDS (none yet)
+  struct Where {
+    uint32_t s, g, v;
+  };
+  auto where = [&](uint32_t t) -> Where {
+    const uint32_t i = t / a.tps;
+    // readfirstlane: where the compiler merges these with a copy made under a lane predicate they come back
+    // as vector values; stripe and segment (and every address made from them) belong in SGPRs
+    return {static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(const_table(a.order)[i])),
+            static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(const_table(a.seg_of)[i])),
+            (t - i * a.tps) * kBlock + threadIdx.x};
+  };
+  // a prefetched tile may belong to another segment than the resident one:
+  // its source offsets come from its own record
+  auto load = [&](uint32_t t, u32x4(&d)[K]) {
+    const Where w = where(t);
+    if (w.v < a.nvec) {
+      const auto *sg = const_table(a.segs) + w.g;
+      const uint8_t *sb = a.base + static_cast<int64_t>(w.s) * a.stripe_stride;
+      // uniform 64-bit base + one 32-bit lane offset (chunks of a stripe lie within 4 GiB)
+      const uint32_t vo = w.v * 16u;
+#pragma unroll
+      for (int j = 0; j < K; j++) d[j] = ld_stream(sb + sg->src_off[j] + vo);
+    }
+  };
+  auto run = [&](uint32_t t, const u32x4(&d)[K]) {
+    const Where w = where(t);
+    const auto *sg = const_table(a.segs) + w.g;
+    const int rows = static_cast<int>(sg->rows);
+    if (w.g != resident) {  // workgroup-uniform
+      // no wave may still be looking up the previous tile; LDS-only fences, so
+      // the loads and stores in flight are not drained (tile_loop's ring_barrier)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      __builtin_amdgcn_s_barrier();
+      build_tables<R>(a.segs[w.g].coef, K, rows, tab);  // rows >= the record's: zero products
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+      resident = w.g;
+    }
+    if (w.v < a.nvec) {
+      uint32_t acc[16];
+      lookup_sources<K, R>(tl, d, acc);
+      uint8_t *db = a.base + static_cast<int64_t>(w.s) * a.stripe_stride;
+      const uint32_t vo = w.v * 16u;
+      const uint32_t o0 = sg->dst_off[0], o1 = sg->dst_off[1], o2 = sg->dst_off[2], o3 = sg->dst_off[3];
+      store_rows(acc, rows, [=](int r) { return db + (r == 0 ? o0 : r == 1 ? o1 : r == 2 ? o2 : o3) + vo; });
+    }
+  };
+  // wave 0 (lane 0 = the tile's first vector) always issues its K loads: every tile has at least one vector
+  tile_loop<K, PF, true, true>(load, run, a.ntiles, a.queue_slot, a.tiles_per_grab, tab + kLds / 4);
+}
+
 // Runtime-k vector kernel (k > kMaxTemplK), R = 1 tables, sources in groups of 4.
 template <bool GATHER>
 __global__ __launch_bounds__(kBlock) void k_mul_vec_dyn(const MulArgs a) {
@@ -947,6 +1038,13 @@ constexpr std::array<RaggedFn, sizeof...(Ks)> ragged_table(std::integer_sequence
 }
 const std::array<RaggedFn, kMaxRaggedK> kRagged = ragged_table(std::make_integer_sequence<int, kMaxRaggedK>{});
 
+using MixedFn = void (*)(MixedArgs);
+template <int... Ks>
+constexpr std::array<MixedFn, sizeof...(Ks)> mixed_table(std::integer_sequence<int, Ks...>) {
+  return {{&k_mul_mixed<Ks + 1, default_r(Ks + 1)>...}};
+}
+const std::array<MixedFn, kMaxRaggedK> kMixed = mixed_table(std::make_integer_sequence<int, kMaxRaggedK>{});
+
 int hip_fail(hipError_t e, const char *what) {
   return set_error(NXEC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
@@ -998,6 +1096,9 @@ void list_kernels(std::vector<KernelLds> &out) {
     for (const ScrubTable &t : rows) list_table(out, t, "k_scrub_vec", scrub_vec_lds);
   out.push_back({reinterpret_cast<const void *>(&k_scrub_bytes), "k_scrub_bytes", bytes_lds(NXEC_MAX_K), false});
   list_table(out, kRagged, "k_mul_ragged", ragged_lds);
+  // the mixed kernels' tables start at dynamic LDS byte 0: no static LDS
+  for (int k = 1; k <= kMaxRaggedK; k++)
+    out.push_back({reinterpret_cast<const void *>(kMixed[k - 1]), "k_mul_mixed", mixed_lds(k), true});
 }
 
 }  // namespace
@@ -1050,6 +1151,11 @@ void (*scrub_kernel(int kd, int rows, bool full, int *lds_bytes))(ScrubArgs) {
 const void *ragged_kernel(int k, int *lds_bytes) {
   *lds_bytes = ragged_lds(k);
   return reinterpret_cast<const void *>(kRagged[k - 1]);
+}
+
+const void *mixed_kernel(int k, int *lds_bytes) {
+  *lds_bytes = mixed_lds(k);
+  return reinterpret_cast<const void *>(kMixed[k - 1]);
 }
 
 const std::vector<KernelLds> &kernel_lds_list() {
@@ -1141,6 +1247,7 @@ struct QueueLaunch {
   int64_t grid;
   int lds;
   int32_t slot;
+  const char *tail = nullptr;  // family-specific keys after the slot
 };
 
 void record_launch(const QueueLaunch &l) {
@@ -1151,7 +1258,8 @@ void record_launch(const QueueLaunch &l) {
   if (l.full >= 0) n += std::snprintf(s + n, cap - n, " full=%d", l.full);
   n += std::snprintf(s + n, cap - n, " pf=%d q=%d tpg=%u", l.pf, l.q, l.tpg);
   if (l.sg) n += std::snprintf(s + n, cap - n, " sg=%u", l.sg);
-  std::snprintf(s + n, cap - n, " grid=%lld slot=%d", static_cast<long long>(l.grid), l.slot);
+  n += std::snprintf(s + n, cap - n, " grid=%lld slot=%d", static_cast<long long>(l.grid), l.slot);
+  if (l.tail) std::snprintf(s + n, cap - n, " %s", l.tail);
   launch_log_append("%s", s);
 }
 
@@ -1355,6 +1463,32 @@ int launch_mul_ragged(int rows, int k, const uint8_t *coeffs, const ListStripe *
     if (int rc = queue_launch(kRagged[k - 1], a, a.queue_slot, l, static_cast<hipStream_t>(stream))) return rc;
   }
   return NXEC_OK;
+}
+
+int launch_mul_mixed(int k, uint8_t *base, int64_t stripe_stride, int64_t len, const MixedSeg *d_segs,
+                     const uint32_t *d_order, const uint32_t *d_seg_of, int64_t nitems, int64_t nsegs, int64_t ncoded,
+                     int num_cus, void *stream) {
+  if (nitems <= 0 || len <= 0) return NXEC_OK;
+  if (k < 1 || k > kMaxRaggedK) return set_error(NXEC_ERR_INVALID, "mixed launch: k=%d unsupported", k);
+  const int64_t nvec = len / 16, tps = (nvec + kBlock - 1) / kBlock;
+  if (len % 16 || nvec >= (int64_t(1) << 32) || tps * nitems >= (int64_t(1) << 32))
+    return set_error(NXEC_ERR_INVALID, "mixed launch: too many tiles or a sub-16-byte tail");
+  MixedArgs a{};
+  a.base = base;
+  a.stripe_stride = stripe_stride;
+  a.segs = d_segs;
+  a.order = d_order;
+  a.seg_of = d_seg_of;
+  a.tps = static_cast<uint32_t>(tps);
+  a.nvec = static_cast<uint32_t>(nvec);
+  a.ntiles = static_cast<uint32_t>(tps * nitems);
+  a.tiles_per_grab = tiles_per_grab(k, kMaxRowsPerPass, 0);
+  char tail[64];
+  std::snprintf(tail, sizeof tail, "segs=%lld stripes=%lld", static_cast<long long>(nsegs),
+                static_cast<long long>(ncoded));
+  QueueLaunch l{"k_mul_mixed", "k", k, kMaxRowsPerPass, default_r(k), -1, -1, -1, ragged_prefetch(k), 1,
+                a.tiles_per_grab, 0, std::min<int64_t>(num_cus, a.ntiles), mixed_lds(k), 0, tail};
+  return queue_launch(kMixed[k - 1], a, a.queue_slot, l, static_cast<hipStream_t>(stream));
 }
 
 int launch_pad_chunks(const PadChunks *d_items, const uint32_t *d_bstart, int64_t nitems, int64_t nblocks,

@@ -206,6 +206,102 @@ int nxec_rs_recover_stripes(nxec_ctx_t *ctx, int n, int k, const int32_t *failed
                           d_stripes, failed, chunk_stride, stripe_stride, nullptr, len, nstripes, stream);
 }
 
+// By-runs path of the mixed recover: one nxec_rs_recover_stripes per maximal
+// run of consecutive stripes with equal pattern (any k, alignment and length).
+static int recover_mixed_by_runs(nxec_ctx_t *ctx, int n, int k, const MixedPlan &plan, unsigned char *d_stripes,
+                                 int64_t cs, int64_t ss, int64_t len, int64_t nstripes, void *stream) {
+  for (int64_t s0 = 0; s0 < nstripes;) {
+    const int32_t pi = plan.pattern_of[s0];
+    int64_t s1 = s0 + 1;
+    while (s1 < nstripes && plan.pattern_of[s1] == pi) s1++;
+    if (pi >= 0) {
+      const std::vector<int32_t> &e = plan.patterns[pi].erased;
+      if (int rc = nxec_rs_recover_stripes(ctx, n, k, e.data(), static_cast<int>(e.size()), d_stripes + s0 * ss, cs,
+                                           ss, len, s1 - s0, stream))
+        return rc;
+    }
+    s0 = s1;
+  }
+  return NXEC_OK;
+}
+
+// One-launch path: the plan's tables staged in a context slot that the stream
+// releases with an event (no host synchronisation on the caller's stream).
+static int recover_mixed_one_launch(nxec_ctx_t *ctx, int k, const MixedPlan &plan, unsigned char *d_stripes,
+                                    int64_t cs, int64_t ss, int64_t len, hipStream_t st) {
+  std::vector<MixedSeg> segs;
+  std::vector<uint32_t> order, seg_of;
+  mixed_tables(plan, k, cs, segs, order, seg_of);
+  const size_t seg_bytes = segs.size() * sizeof(MixedSeg);
+  const size_t item_bytes = (order.size() * sizeof(uint32_t) + 15) / 16 * 16;
+  Slot *slot = nullptr;
+  int rc = acquire_slot(ctx, seg_bytes + 2 * item_bytes, &slot, true);
+  if (rc) return rc;
+  // the slot's staging may still be in use by an earlier call on its own stream
+  rc = hip_check(hipStreamSynchronize(slot->stream), "slot sync");
+  if (!rc && !slot->busy) rc = hip_check(hipEventCreateWithFlags(&slot->busy, hipEventDisableTiming), "slot event");
+  if (!rc) {
+    std::memcpy(slot->h, segs.data(), seg_bytes);
+    std::memcpy(slot->h + seg_bytes, order.data(), order.size() * sizeof(uint32_t));
+    std::memcpy(slot->h + seg_bytes + item_bytes, seg_of.data(), seg_of.size() * sizeof(uint32_t));
+    rc = hip_check(hipMemcpyAsync(slot->d, slot->h, seg_bytes + 2 * item_bytes, hipMemcpyHostToDevice, st), "tables H2D");
+  }
+  hipEvent_t kt[2];
+  kt_begin(ctx, st, kt);
+  const int64_t per = max_stripes_per_launch(len / 16), nitems = static_cast<int64_t>(order.size());
+  for (int64_t i0 = 0; i0 < nitems && !rc; i0 += per)
+    rc = launch_mul_mixed(k, d_stripes, ss, len, reinterpret_cast<const MixedSeg *>(slot->d),
+                          reinterpret_cast<const uint32_t *>(slot->d + seg_bytes) + i0,
+                          reinterpret_cast<const uint32_t *>(slot->d + seg_bytes + item_bytes) + i0,
+                          std::min(per, nitems - i0), static_cast<int64_t>(segs.size()), plan.ncoded, ctx->num_cus, st);
+  kt_end(ctx, kt, st);
+  // the tables stay in the slot until the stream gets past the launches
+  if (!rc) rc = hip_check(hipEventRecord(slot->busy, st), "slot event record");
+  slot->busy_set = !rc;
+  if (rc) (void)hipStreamSynchronize(st);
+  release_slot(ctx, slot);
+  return rc;
+}
+
+int nxec_rs_recover_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned char *alive,
+                                  unsigned char *d_stripes, int64_t chunk_stride, int64_t stripe_stride, int64_t len,
+                                  int64_t nstripes, int32_t *result, void *stream) {
+  if (!ctx) return set_error(NXEC_ERR_INVALID, "null context");
+  if (!valid_nk(n, k)) return set_error(NXEC_ERR_INVALID, "invalid (n,k)=(%d,%d)", n, k);
+  if (len < 0 || nstripes < 0) return set_error(NXEC_ERR_INVALID, "negative len or nstripes");
+  if (!alive && nstripes > 0) return set_error(NXEC_ERR_INVALID, "mixed recover: null alive map");
+  // stripe ids are 32-bit in the device tables: larger batches go block by block
+  constexpr int64_t kBlockStripes = int64_t(1) << 31;
+  if (nstripes > kBlockStripes) {
+    for (int64_t s0 = 0; s0 < nstripes; s0 += kBlockStripes)
+      if (int rc = nxec_rs_recover_stripes_mixed(ctx, n, k, alive + s0 * n, d_stripes ? d_stripes + s0 * stripe_stride : nullptr,
+                                                 chunk_stride, stripe_stride, len, std::min(kBlockStripes, nstripes - s0),
+                                                 result ? result + s0 : nullptr, stream))
+        return rc;
+    return NXEC_OK;
+  }
+  std::vector<int32_t> verdict(static_cast<size_t>(nstripes));
+  MixedPlan plan;
+  mixed_plan(n, k, alive, nstripes, verdict.data(), &plan);
+  const bool work = plan.ncoded > 0 && len > 0;
+  if (work && !d_stripes) return set_error(NXEC_ERR_INVALID, "null stripe buffer");
+  // chunk byte offsets inside a stripe stay 32-bit (the kernels' scalar address math)
+  if (work && (chunk_stride < 0 || static_cast<int64_t>(n - 1) * chunk_stride + len > (int64_t(1) << 32) - 1))
+    return set_error(NXEC_ERR_INVALID, "mixed recover: chunk offset out of range (chunks of a stripe must lie within 4 GiB)");
+  int rc = NXEC_OK;
+  if (work) {
+    if ((rc = ensure_device(ctx->device))) return rc;
+    const bool one_launch = k <= kMaxRaggedK && aligned16(d_stripes) && chunk_stride % 16 == 0 &&
+                            stripe_stride % 16 == 0 && len % 16 == 0;
+    rc = one_launch ? recover_mixed_one_launch(ctx, k, plan, d_stripes, chunk_stride, stripe_stride, len,
+                                               pick_stream(ctx, stream))
+                    : recover_mixed_by_runs(ctx, n, k, plan, d_stripes, chunk_stride, stripe_stride, len, nstripes,
+                                            stream);
+  }
+  if (result && nstripes > 0) std::memcpy(result, verdict.data(), verdict.size() * sizeof(int32_t));
+  return rc;
+}
+
 int nxec_rs_scrub_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripes, int64_t chunk_stride,
                           int64_t stripe_stride, int64_t len, int64_t nstripes, int flags, int32_t *d_status,
                           unsigned long long *d_nbad, void *stream) {

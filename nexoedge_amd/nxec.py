@@ -98,6 +98,30 @@ def syndrome_locate(n: int, k: int, syndrome) -> tuple:
     return chunk.value, err.value
 
 
+RECOVER_LOST = _lib.NXEC_RECOVER_LOST
+RECOVER_SINGULAR = _lib.NXEC_RECOVER_SINGULAR
+
+
+def _alive_map(n: int, alive) -> np.ndarray:
+    a = np.ascontiguousarray(alive, dtype=np.uint8)
+    if a.size % n:
+        raise ValueError(f"alive map of {a.size} bytes is not [nstripes][{n}]")
+    return a
+
+
+def rs_recover_mixed_plan(n: int, k: int, alive):
+    """nxec_rs_recover_mixed_plan, the host half of Context.rs_recover_mixed (no device): `alive` is
+    [nstripes][n], non-zero = chunk present and trusted.  Returns (int32 result per stripe: chunks to
+    rebuild, RECOVER_LOST or RECOVER_SINGULAR; distinct decodable patterns; segments; coded stripes)."""
+    a = _alive_map(n, alive)
+    ns = a.size // n if n > 0 else 0
+    res = np.zeros(ns, dtype=np.int32)
+    npat, nseg, ncoded = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib.nxec_rs_recover_mixed_plan(n, k, _u8(a), ns, C.c_void_p(res.ctypes.data), C.byref(npat), C.byref(nseg),
+                                         C.byref(ncoded)), "nxec_rs_recover_mixed_plan")
+    return res, npat.value, nseg.value, ncoded.value
+
+
 LAYOUT_RECOVER_HEAVY = 1
 OBJECTS_TAIL_INPLACE = 1  # nxec_encode_objects_ex: only the partial last-stripe chunk to the tail arena
 OBJECTS_ASYNC = 2  # nxec_encode_objects_ex: return once queued on the stream
@@ -509,6 +533,20 @@ class Context:
         check(lib.nxec_rs_recover_stripes(C.c_void_p(self.ptr), n, k, fp, len(failed), C.c_void_p(int(stripes)),
                                           chunk_stride, stripe_stride, length, nstripes, stream),
               "nxec_rs_recover_stripes")
+
+    def rs_recover_mixed(self, n: int, k: int, alive, stripes: int, chunk_stride: int, stripe_stride: int,
+                         length: int, nstripes: int, stream=None) -> np.ndarray:
+        """nxec_rs_recover_stripes_mixed: every stripe rebuilds its own erased chunks (`alive` [nstripes][n],
+        0 = erased, e.g. a downloaded ok map of md5_verify_chunks) in place.  Asynchronous on `stream`;
+        `alive` may be reused at once.  Returns the int32 result per stripe (see rs_recover_mixed_plan)."""
+        a = _alive_map(n, alive)
+        if a.size != n * nstripes:
+            raise ValueError(f"alive map of {a.size} bytes for {nstripes} stripes of {n} chunks")
+        res = np.zeros(nstripes, dtype=np.int32)
+        check(lib.nxec_rs_recover_stripes_mixed(C.c_void_p(self.ptr), n, k, _u8(a), C.c_void_p(int(stripes)),
+                                                chunk_stride, stripe_stride, length, nstripes,
+                                                C.c_void_p(res.ctypes.data), stream), "nxec_rs_recover_stripes_mixed")
+        return res
 
     def rs_scrub_stripes(self, n: int, k: int, stripes: int, chunk_stride: int, stripe_stride: int, length: int,
                          nstripes: int, status: int, flags: int = 0, nbad=None, stream=None) -> None:
