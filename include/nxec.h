@@ -277,6 +277,83 @@ int nxec_rs_recover_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned 
 int nxec_rs_recover_mixed_plan(int n, int k, const unsigned char *alive, int64_t nstripes, int32_t *result,
                                int64_t *npatterns, int64_t *nsegments, int64_t *ncoded);
 
+/* Delta update: overwrite byte ranges of data chunks of coded stripes and
+ * bring the parity along, without reading the other data chunks.  The code is
+ * linear, so for an update of data chunk j of a stripe over the byte columns
+ * [offset, offset + length):
+ *   delta   = new ^ old
+ *   d_j[i]  = new[i]
+ *   p_r[i] ^= c(r,j) (x) delta[i]        for every parity row r < n-k,
+ * with c the parity rows of nxec_gf_gen_rs_matrix(n, k): 2 + (n-k) bytes read
+ * and 1 + (n-k) written per updated byte, whatever k and len are.
+ *
+ * After the call every updated data byte holds its new value and every parity
+ * byte of an updated column has been XORed with c(r,j) (x) (new ^ old).  The
+ * syndrome (nxec_rs_scrub_stripes) of every byte of every stripe is what it
+ * was before: a stripe that was a codeword stays one, and is then byte for
+ * byte what overwriting the data and calling nxec_rs_encode_stripes gives; a
+ * stripe the scrub locates as corrupt in chunk c is still located in chunk c.
+ * No byte outside the updated columns of the updated data chunk and of the
+ * n-k parity chunks is read or written; stride padding is never written;
+ * d_new is only read.  The digests of the 1 + (n-k) touched chunks are not
+ * refreshed (nxec_md5_chunks re-hashes them).
+ *
+ * `updates` (HOST) is read before the call returns and may be reused at once.
+ * The device work is asynchronous on `stream` with no host synchronisation
+ * inside: the planner's tables are staged in a context slot released with an
+ * event, as nxec_rs_recover_stripes_mixed stages its tables.  d_new must stay
+ * valid until the stream reaches that point.
+ *
+ * Two updates whose byte ranges intersect on the same (stripe, chunk) have no
+ * defined order: an error.  Updates of different chunks of one stripe over
+ * intersecting columns are legal; both read-modify-write the same parity
+ * bytes, so the planner puts them in different rounds.  A round is a set of
+ * updates whose stripes and column ranges are pairwise disjoint, found by
+ * greedy interval colouring per stripe (at most k rounds, since same-chunk
+ * intersections are refused); each round is one stream-ordered launch per
+ * pass of <= 4 parity rows.  A batch without such intersections is exactly
+ * one round.
+ *
+ * Two kinds of work item, shown by the launch record (nxec_debug_launch_log):
+ *   vector tiles  k <= 19 and d_stripes, chunk_stride and stripe_stride
+ *                 16-byte aligned: the body of an update, its columns
+ *                 [rup16(offset), rdn16(offset + length)), where the matching
+ *                 address in d_new is 16-byte aligned, in tiles of up to 1024
+ *                 consecutive vectors of one update through the queue-driven
+ *                 kernel k_update_vec (every pass recomputes the delta from
+ *                 the old data, so only the last pass stores the new data);
+ *   byte items    everything else (heads and tails shorter than 16 bytes,
+ *                 updates whose d_new alignment does not match, unaligned
+ *                 layouts, k > 19): one thread per byte (k_update_bytes), a
+ *                 launch of its own after the round's vector launch.  Correct
+ *                 for every shape the library accepts.
+ *
+ * NULL ctx, invalid (n,k), negative sizes, NULL updates with nupdates > 0, a
+ * stripe, chunk or range outside its bounds, reserved != 0, a same-chunk
+ * intersection, a d_new range that intersects [d_stripes, d_stripes +
+ * nstripes*stripe_stride), NULL d_new with length > 0, NULL d_stripes when
+ * there is work to do, or chunk offsets of a stripe beyond 4 GiB give
+ * NXEC_ERR_INVALID before any device use.  nupdates == 0, or lengths that are
+ * all 0, launch nothing.  With n == k the data is overwritten and nothing
+ * else happens. */
+typedef struct nxec_update {
+  int64_t stripe;             /* 0 .. nstripes-1 */
+  int32_t chunk;              /* data chunk id, 0 .. k-1 */
+  int32_t reserved;           /* 0 */
+  int64_t offset, length;     /* byte range inside the chunk: offset >= 0, length >= 0, offset+length <= len */
+  const unsigned char *d_new; /* DEVICE: `length` new bytes */
+} nxec_update;
+int nxec_rs_update_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripes, int64_t chunk_stride,
+                           int64_t stripe_stride, int64_t len, int64_t nstripes, const nxec_update *updates,
+                           int64_t nupdates, void *stream);
+/* The host half alone (pure, no device), with the batch's device address as an
+ * integer: the same validation, then *nrounds = rounds, *nvec_tiles = vector
+ * tiles and *nbyte_items = byte items over all rounds (each may be NULL; a
+ * round of more than 4 parity rows runs its tiles and items once per pass). */
+int nxec_rs_update_plan(int n, int k, int64_t chunk_stride, int64_t stripe_stride, int64_t len, int64_t nstripes,
+                        uintptr_t stripes_addr, const nxec_update *updates, int64_t nupdates, int64_t *nrounds,
+                        int64_t *nvec_tiles, int64_t *nbyte_items);
+
 /* Parity scrub: are the n chunks of every stripe still a codeword, and if
  * not, which chunk is wrong?  Needs no stored digests, and sees a torn stripe
  * (data rewritten, parity not) that nxec_md5_verify_chunks cannot.

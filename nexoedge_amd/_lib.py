@@ -63,6 +63,9 @@ _PROTOS = {
     "nxec_rs_recover_stripes_mixed": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, i64, i64, i64, i64, vp, vp]),
     "nxec_rs_recover_mixed_plan": (C.c_int, [C.c_int, C.c_int, vp, i64, vp, C.POINTER(i64), C.POINTER(i64),
                                              C.POINTER(i64)]),
+    "nxec_rs_update_stripes": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, i64, i64, i64, vp, i64, vp]),
+    "nxec_rs_update_plan": (C.c_int, [C.c_int, C.c_int, i64, i64, i64, i64, C.c_size_t, vp, i64, C.POINTER(i64),
+                                      C.POINTER(i64), C.POINTER(i64)]),
     "nxec_rs_scrub_stripes": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, i64, i64, i64, C.c_int, vp, vp, vp]),
     "nxec_rs_syndrome_locate": (C.c_int, [C.c_int, C.c_int, vp, i32p, u8p]),
     "nxec_rs_decode_stripes": (
@@ -183,6 +186,12 @@ class AgentReq(C.Structure):
     """struct nxec_agent_req of include/nxec.h"""
     _fields_ = [("ninputs", C.c_int), ("noutputs", C.c_int), ("matrix", vp), ("inputs", vp), ("outputs", vp),
                 ("md5", vp), ("md5_inputs", vp)]
+
+
+class Update(C.Structure):
+    """struct nxec_update of include/nxec.h"""
+    _fields_ = [("stripe", C.c_int64), ("chunk", C.c_int32), ("reserved", C.c_int32), ("offset", C.c_int64),
+                ("length", C.c_int64), ("d_new", vp)]
 
 
 for _name, (_res, _args) in _PROTOS.items():

@@ -244,6 +244,60 @@ const void *mixed_kernel(int k, int *lds_bytes);
 int launch_mul_mixed(int k, uint8_t *base, int64_t stripe_stride, int64_t len, const MixedSeg *d_segs,
                      const uint32_t *d_order, const uint32_t *d_seg_of, int64_t nitems, int64_t nsegs, int64_t ncoded,
                      int num_cus, void *stream);
+// Delta update (nxec_rs_update_stripes): byte ranges of data chunks are
+// overwritten and the parity follows by c(r,j) (x) (new ^ old).  Host half
+// (nxec_update_host.cpp, pure arithmetic, no device): validation, the rounds,
+// the split into vector tiles and byte items, and the device tables.
+//
+// One work item: `count` consecutive 16-byte vectors (a vector item: col and
+// d_new 16-byte aligned) or bytes (a byte item) of data chunk `chunk` of one
+// stripe, starting at byte column `col` of the chunk.  The data byte of column
+// c lies at base + stripe_off + chunk*chunk_stride + c, parity row r's at
+// base + stripe_off + (k + r)*chunk_stride + c; all below 4 GiB past the stripe.
+struct UpdateItem {
+  const uint8_t *d_new;  // DEVICE: the new bytes of the item, from column col on
+  int64_t stripe_off;    // stripe * stripe_stride
+  uint32_t col, chunk;
+  uint32_t first;  // vector item: its first tile among the round's tiles
+  uint32_t count;
+};
+static_assert(sizeof(UpdateItem) == 32, "item records are staged 16-byte aligned");
+// A round: updates whose (stripe, column range) are pairwise disjoint, so no
+// two of its items touch the same byte.  Its items, tile map and byte prefix
+// are slices of the plan's tables.
+struct UpdateRound {
+  size_t vec_item0, byte_item0;  // first vector item / byte item in UpdatePlan::items
+  size_t tile0;                  // first entry in tile_item
+  size_t prefix0;                // first entry in byte_prefix (nbyte_items + 1 entries)
+  int64_t nupdates;              // updates with length > 0 in the round
+  int64_t nvec_items, ntiles, nbyte_items, nbytes;
+};
+struct UpdatePlan {
+  std::vector<UpdateItem> items;     // per round: its vector items, then its byte items
+  std::vector<uint32_t> tile_item;   // per round: tile t -> index into items (tile t - item.first of the item)
+  std::vector<int64_t> byte_prefix;  // per round: first byte index of each byte item, then the round's bytes
+  std::vector<UpdateRound> rounds;
+  int64_t nvec_tiles = 0, nbyte_items = 0;  // over all rounds
+};
+constexpr int kUpdateTileVecs = 1024;  // vectors per tile: one per thread of the vector kernel's workgroup
+// Validates everything nxec_rs_update_stripes documents except the context and
+// fills *plan (may be NULL); NXEC_OK or NXEC_ERR_INVALID.  stripes_addr is the
+// batch's device address as an integer (alignment, and d_new must stay clear of it).
+int update_plan(int n, int k, int64_t chunk_stride, int64_t stripe_stride, int64_t len, int64_t nstripes,
+                uintptr_t stripes_addr, const nxec_update *updates, int64_t nupdates, UpdatePlan *plan);
+// The vector kernel of k <= kMaxRaggedK / the byte kernel of k <= NXEC_MAX_K and the dynamic LDS the launch asks for.
+const void *update_vec_kernel(int k, int *lds_bytes);
+const void *update_bytes_kernel(int k, int *lds_bytes);
+// One row pass (rows <= 4 parity rows from row0 on, coef rows x k; rows == 0
+// with n == k) over one round's tiles / byte items; tables in device memory,
+// tile_item / byte_prefix already at the round's slice.  `last`: the pass that
+// also stores the new data.  nupdates, round and pass only go to the launch record.
+int launch_update_vec(int k, int rows, int row0, const uint8_t *coef, uint8_t *base, int64_t chunk_stride,
+                      const UpdateItem *d_items, const uint32_t *d_tile_item, int64_t ntiles, bool last,
+                      int64_t nupdates, int round, int pass, int num_cus, void *stream);
+int launch_update_bytes(int k, int rows, int row0, const uint8_t *coef, uint8_t *base, int64_t chunk_stride,
+                        const UpdateItem *d_items, const int64_t *d_byte_prefix, int64_t nitems, int64_t nbytes,
+                        bool last, int round, int pass, int num_cus, void *stream);
 // Last stripe of an object into the aligned tail arena: dst + j*cls (j < k)
 // receives object bytes [j*cl, (j+1)*cl) of src (zeros past rem) then zeros
 // up to cls (a multiple of 16 >= cl).  Item i owns 256-thread blocks

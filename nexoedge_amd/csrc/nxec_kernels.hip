@@ -647,6 +647,127 @@ __global__ __launch_bounds__(kBlock) void k_mul_mixed(const MixedArgs a) {
   tile_loop<K, PF, true, true>(load, run, a.ntiles, a.queue_slot, a.tiles_per_grab, tab + kLds / 4);
 }
 
+// --- delta update (nxec_rs_update_stripes) ---
+// Byte ranges of data chunks are overwritten and the parity follows:
+// p_r ^= c(r,j) (x) (new ^ old).  One pass covers <= 4 parity rows of one
+// round (updates whose stripes and column ranges are pairwise disjoint, the
+// host planner's invariant).  Every pass recomputes the delta from the old
+// data, so only the last pass of a round stores the new data.
+struct UpdateArgs {
+  uint8_t *base;
+  const UpdateItem *__restrict__ items;
+  const uint32_t *__restrict__ tile_item;  // vector kernel: tile -> item
+  const int64_t *__restrict__ byte_prefix;  // byte kernel: first byte index of each item, then the total
+  int64_t nitems, nbytes;                   // byte kernel
+  uint32_t ntiles;
+  int32_t k, rows, last, queue_slot;
+  uint32_t tiles_per_grab;
+  uint32_t chunk_stride;
+  uint32_t par_off[kMaxRowsPerPass];  // byte offset of the pass's parity chunks inside a stripe
+  uint8_t coef[kMaxRowsPerPass * (NXEC_MAX_K + 1)];  // row-major rows x k
+};
+
+constexpr int update_lds(int k) { return vec_lds(k, default_r(k)); }
+constexpr int kUpdateSrc = 2 + kMaxRowsPerPass;  // a lane's vectors per tile: old data, new data, the parity rows
+static_assert(kUpdateTileVecs == kBlock, "the planner's tiles are one vector per thread");
+
+// The encode tables of the pass's rows for all k columns (k_mul_vec's layout);
+// the column an update multiplies by is a per-tile scalar, so k is not a
+// template parameter: one instantiation per R, launched with update_lds(k).
+// Item, stripe and column stay in SGPRs (const_table at a workgroup-uniform
+// index); only the vector index is per lane.
+//
+// In place under prefetch: tile_loop issues tile t+1's loads before tile t's
+// stores and re-reads the current tile once past the end.  The tiles of one
+// launch are pairwise disjoint in every byte they read or write (one round),
+// so no load can see a store of the same launch.
+template <int R>
+__global__ __launch_bounds__(kBlock) void k_update_vec(const UpdateArgs a) {
+  constexpr int K = kUpdateSrc;
+  extern __shared__ uint32_t tab[];
+  build_tables<R>(a.coef, a.k, a.rows, tab);
+  __syncthreads();
+  const char *tl = reinterpret_cast<const char *>(tab) + (threadIdx.x % R) * 4;
+  struct Where {
+    const uint8_t *nw;  // the item's new bytes
+    uint8_t *sb;        // its stripe
+    uint32_t col, chunk, count, v;
+  };
+  auto where = [&](uint32_t t) -> Where {
+    const uint32_t i = __builtin_amdgcn_readfirstlane(const_table(a.tile_item)[t]);
+    const auto *it = const_table(a.items) + i;
+    return {it->d_new,
+            a.base + it->stripe_off,
+            static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(it->col)),
+            static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(it->chunk)),
+            static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(it->count)),
+            (t - static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(it->first))) * kBlock + threadIdx.x};
+  };
+  // d[0] = old data, d[1] = new data, d[2 + r] = parity row r of the pass
+  auto load = [&](uint32_t t, u32x4(&d)[K]) {
+    const Where w = where(t);
+    if (w.v < w.count) {
+      // uniform 64-bit base + one 32-bit lane offset (chunks of a stripe lie within 4 GiB)
+      const uint32_t vo = w.col + w.v * 16u;
+      d[0] = ld_stream(w.sb + w.chunk * a.chunk_stride + vo);
+      d[1] = ld_stream(w.nw + w.v * 16u);
+#pragma unroll
+      for (int r = 0; r < kMaxRowsPerPass; r++)
+        if (r < a.rows) d[2 + r] = ld_stream(w.sb + a.par_off[r] + vo);
+    }
+  };
+  auto run = [&](uint32_t t, const u32x4(&d)[K]) {
+    const Where w = where(t);
+    if (w.v < w.count) {
+      uint32_t acc[16];
+#pragma unroll
+      for (int i = 0; i < 16; i++) acc[i] = 0;
+      lookup16<R>(tl + w.chunk * table_bytes(1, R), d[0] ^ d[1], acc);
+      uint32_t o[4][4];
+      rows_of(acc, o);
+      const uint32_t vo = w.col + w.v * 16u;
+#pragma unroll
+      for (int r = 0; r < kMaxRowsPerPass; r++)
+        if (r < a.rows)
+          st_stream(w.sb + a.par_off[r] + vo, d[2 + r] ^ u32x4{o[r][0], o[r][1], o[r][2], o[r][3]});
+      if (a.last) st_stream(w.sb + w.chunk * a.chunk_stride + vo, d[1]);
+    }
+  };
+  // QWAIT_K = false: a pass of fewer than 4 rows issues fewer than K loads per
+  // tile, so "at most K outstanding" would not prove that the grab returned;
+  // the publishing thread waits for all of its vector-memory operations instead
+  tile_loop<K, true, true, false>(load, run, a.ntiles, a.queue_slot, a.tiles_per_grab,
+                                  tab + table_bytes(a.k, R) / 4);
+}
+
+// Byte items: one thread per byte, R = 1 tables, any k and alignment.  The
+// items of one round touch pairwise disjoint bytes, so a byte store never
+// meets a neighbour's.
+__global__ __launch_bounds__(256) void k_update_bytes(const UpdateArgs a) {
+  extern __shared__ uint32_t tab[];
+  const int k = a.k;
+  build_tables<1>(a.coef, k, a.rows, tab);
+  __syncthreads();
+  for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < a.nbytes;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    int64_t lo = 0, hi = a.nitems - 1;  // last item with byte_prefix <= i
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) >> 1;
+      if (a.byte_prefix[mid] <= i) lo = mid;
+      else hi = mid - 1;
+    }
+    const UpdateItem it = a.items[lo];
+    const int64_t b = i - a.byte_prefix[lo];
+    uint8_t *stripe = a.base + it.stripe_off;
+    const int64_t c = static_cast<int64_t>(it.col) + b;
+    uint8_t *data = stripe + static_cast<int64_t>(it.chunk) * a.chunk_stride + c;
+    const uint8_t nw = it.d_new[b];
+    const uint32_t e = tab[it.chunk * 256 + (*data ^ nw)];
+    for (int r = 0; r < a.rows; r++) stripe[a.par_off[r] + c] ^= static_cast<uint8_t>(e >> (8 * r));
+    if (a.last) *data = nw;
+  }
+}
+
 // Runtime-k vector kernel (k > kMaxTemplK), R = 1 tables, sources in groups of 4.
 template <bool GATHER>
 __global__ __launch_bounds__(kBlock) void k_mul_vec_dyn(const MulArgs a) {
@@ -1045,6 +1166,13 @@ constexpr std::array<MixedFn, sizeof...(Ks)> mixed_table(std::integer_sequence<i
 }
 const std::array<MixedFn, kMaxRaggedK> kMixed = mixed_table(std::make_integer_sequence<int, kMaxRaggedK>{});
 
+// two update kernels, each prepared at the largest k it serves: R = 16 while default_r(k) is 16, R = 8 up to kMaxRaggedK
+using UpdateFn = void (*)(UpdateArgs);
+constexpr int kUpdateMaxK16 = 9;
+static_assert(default_r(kUpdateMaxK16) == 16 && default_r(kUpdateMaxK16 + 1) == 8, "the update kernels follow default_r");
+static_assert(update_lds(kMaxRaggedK) <= kLdsBytes, "the widest update tables and the ring fit");
+UpdateFn update_fn(int k) { return k <= kUpdateMaxK16 ? &k_update_vec<16> : &k_update_vec<8>; }
+
 int hip_fail(hipError_t e, const char *what) {
   return set_error(NXEC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
@@ -1099,6 +1227,10 @@ void list_kernels(std::vector<KernelLds> &out) {
   // the mixed kernels' tables start at dynamic LDS byte 0: no static LDS
   for (int k = 1; k <= kMaxRaggedK; k++)
     out.push_back({reinterpret_cast<const void *>(kMixed[k - 1]), "k_mul_mixed", mixed_lds(k), true});
+  // like them, the update kernels index their tables from dynamic LDS byte 0
+  out.push_back({reinterpret_cast<const void *>(update_fn(kUpdateMaxK16)), "k_update_vec", update_lds(kUpdateMaxK16), true});
+  out.push_back({reinterpret_cast<const void *>(update_fn(kMaxRaggedK)), "k_update_vec", update_lds(kMaxRaggedK), true});
+  out.push_back({reinterpret_cast<const void *>(&k_update_bytes), "k_update_bytes", bytes_lds(NXEC_MAX_K), false});
 }
 
 }  // namespace
@@ -1156,6 +1288,15 @@ const void *ragged_kernel(int k, int *lds_bytes) {
 const void *mixed_kernel(int k, int *lds_bytes) {
   *lds_bytes = mixed_lds(k);
   return reinterpret_cast<const void *>(kMixed[k - 1]);
+}
+
+const void *update_vec_kernel(int k, int *lds_bytes) {
+  *lds_bytes = update_lds(k);
+  return reinterpret_cast<const void *>(update_fn(k));
+}
+const void *update_bytes_kernel(int k, int *lds_bytes) {
+  *lds_bytes = bytes_lds(k);
+  return reinterpret_cast<const void *>(&k_update_bytes);
 }
 
 const std::vector<KernelLds> &kernel_lds_list() {
@@ -1489,6 +1630,66 @@ int launch_mul_mixed(int k, uint8_t *base, int64_t stripe_stride, int64_t len, c
   QueueLaunch l{"k_mul_mixed", "k", k, kMaxRowsPerPass, default_r(k), -1, -1, -1, ragged_prefetch(k), 1,
                 a.tiles_per_grab, 0, std::min<int64_t>(num_cus, a.ntiles), mixed_lds(k), 0, tail};
   return queue_launch(kMixed[k - 1], a, a.queue_slot, l, static_cast<hipStream_t>(stream));
+}
+
+namespace {
+void update_pass(UpdateArgs &a, int k, int rows, int row0, const uint8_t *coef, uint8_t *base, int64_t chunk_stride,
+                 bool last) {
+  a.base = base;
+  a.k = k;
+  a.rows = rows;
+  a.last = last;
+  a.chunk_stride = static_cast<uint32_t>(chunk_stride);
+  for (int r = 0; r < rows; r++) {
+    a.par_off[r] = static_cast<uint32_t>((k + row0 + r) * chunk_stride);
+    for (int j = 0; j < k; j++) a.coef[r * k + j] = coef[static_cast<size_t>(r) * k + j];
+  }
+}
+}  // namespace
+
+int launch_update_vec(int k, int rows, int row0, const uint8_t *coef, uint8_t *base, int64_t chunk_stride,
+                      const UpdateItem *d_items, const uint32_t *d_tile_item, int64_t ntiles, bool last,
+                      int64_t nupdates, int round, int pass, int num_cus, void *stream) {
+  if (ntiles <= 0) return NXEC_OK;
+  if (k < 1 || k > kMaxRaggedK || rows < 0 || rows > kMaxRowsPerPass)
+    return set_error(NXEC_ERR_INVALID, "update launch: k=%d rows=%d unsupported", k, rows);
+  if (ntiles >= (int64_t(1) << 32)) return set_error(NXEC_ERR_INVALID, "update launch: too many tiles");
+  UpdateArgs a{};
+  update_pass(a, k, rows, row0, coef, base, chunk_stride, last);
+  a.items = d_items;
+  a.tile_item = d_tile_item;
+  a.ntiles = static_cast<uint32_t>(ntiles);
+  // a tile moves the old and new data, the new data back on the last pass, and every parity row both ways
+  a.tiles_per_grab = tiles_per_grab(2 + (last ? 1 : 0), 2 * rows, 0);
+  char tail[96];
+  std::snprintf(tail, sizeof tail, "tiles=%lld updates=%lld round=%d pass=%d last=%d", static_cast<long long>(ntiles),
+                static_cast<long long>(nupdates), round, pass, last ? 1 : 0);
+  QueueLaunch l{"k_update_vec", "k", k, rows, default_r(k), -1, -1, -1, 1, 1, a.tiles_per_grab, 0,
+                std::min<int64_t>(num_cus, ntiles), update_lds(k), 0, tail};
+  return queue_launch(update_fn(k), a, a.queue_slot, l, static_cast<hipStream_t>(stream));
+}
+
+int launch_update_bytes(int k, int rows, int row0, const uint8_t *coef, uint8_t *base, int64_t chunk_stride,
+                        const UpdateItem *d_items, const int64_t *d_byte_prefix, int64_t nitems, int64_t nbytes,
+                        bool last, int round, int pass, int num_cus, void *stream) {
+  if (nitems <= 0 || nbytes <= 0) return NXEC_OK;
+  if (k < 1 || k > NXEC_MAX_K || rows < 0 || rows > kMaxRowsPerPass)
+    return set_error(NXEC_ERR_INVALID, "update launch: k=%d rows=%d unsupported", k, rows);
+  UpdateArgs a{};
+  update_pass(a, k, rows, row0, coef, base, chunk_stride, last);
+  a.items = d_items;
+  a.byte_prefix = d_byte_prefix;
+  a.nitems = nitems;
+  a.nbytes = nbytes;
+  a.queue_slot = -1;
+  const int64_t blocks = std::min<int64_t>((nbytes + 255) / 256, static_cast<int64_t>(num_cus) * 8);
+  if (launch_log_on())
+    launch_log_append("family=k_update_bytes k=%d rows=%d r=1 grid=%lld items=%lld round=%d pass=%d last=%d", k, rows,
+                      static_cast<long long>(blocks), static_cast<long long>(nitems), round, pass, last ? 1 : 0);
+  hipLaunchKernelGGL(k_update_bytes, dim3(static_cast<unsigned>(blocks)), dim3(256), bytes_lds(k),
+                     static_cast<hipStream_t>(stream), a);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? NXEC_OK : hip_fail(e, "launch k_update_bytes");
 }
 
 int launch_pad_chunks(const PadChunks *d_items, const uint32_t *d_bstart, int64_t nitems, int64_t nblocks,

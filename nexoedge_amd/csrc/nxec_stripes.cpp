@@ -302,6 +302,69 @@ int nxec_rs_recover_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned 
   return rc;
 }
 
+// Delta update: the planner's tables staged in a context slot that the stream
+// releases with an event (recover_mixed_one_launch's scheme), then per round
+// and per pass of <= 4 parity rows the vector launch and the byte launch.
+int nxec_rs_update_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripes, int64_t chunk_stride,
+                           int64_t stripe_stride, int64_t len, int64_t nstripes, const nxec_update *updates,
+                           int64_t nupdates, void *stream) {
+  if (!ctx) return set_error(NXEC_ERR_INVALID, "null context");
+  UpdatePlan plan;
+  int rc = update_plan(n, k, chunk_stride, stripe_stride, len, nstripes, reinterpret_cast<uintptr_t>(d_stripes),
+                       updates, nupdates, &plan);
+  if (rc) return rc;
+  if (plan.rounds.empty()) return NXEC_OK;
+  if (!d_stripes) return set_error(NXEC_ERR_INVALID, "null stripe buffer");
+  if ((rc = ensure_device(ctx->device))) return rc;
+  hipStream_t st = pick_stream(ctx, stream);
+  std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
+  nxec_gf_gen_rs_matrix(enc.data(), n, k);
+  const uint8_t *parity = enc.data() + static_cast<size_t>(k) * k;  // (n-k) x k
+
+  const size_t item_bytes = plan.items.size() * sizeof(UpdateItem);
+  const size_t prefix_bytes = (plan.byte_prefix.size() * sizeof(int64_t) + 15) / 16 * 16;
+  const size_t tile_bytes = (plan.tile_item.size() * sizeof(uint32_t) + 15) / 16 * 16;
+  const size_t total = item_bytes + prefix_bytes + tile_bytes;
+  Slot *slot = nullptr;
+  if ((rc = acquire_slot(ctx, total, &slot, true))) return rc;
+  // the slot's staging may still be in use by an earlier call on its own stream
+  rc = hip_check(hipStreamSynchronize(slot->stream), "slot sync");
+  if (!rc && !slot->busy) rc = hip_check(hipEventCreateWithFlags(&slot->busy, hipEventDisableTiming), "slot event");
+  if (!rc) {
+    std::memcpy(slot->h, plan.items.data(), item_bytes);
+    std::memcpy(slot->h + item_bytes, plan.byte_prefix.data(), plan.byte_prefix.size() * sizeof(int64_t));
+    std::memcpy(slot->h + item_bytes + prefix_bytes, plan.tile_item.data(), plan.tile_item.size() * sizeof(uint32_t));
+    rc = hip_check(hipMemcpyAsync(slot->d, slot->h, total, hipMemcpyHostToDevice, st), "tables H2D");
+  }
+  const UpdateItem *d_items = reinterpret_cast<const UpdateItem *>(slot->d);
+  const int64_t *d_prefix = reinterpret_cast<const int64_t *>(slot->d + item_bytes);
+  const uint32_t *d_tiles = reinterpret_cast<const uint32_t *>(slot->d + item_bytes + prefix_bytes);
+  hipEvent_t kt[2];
+  kt_begin(ctx, st, kt);
+  const int m = n - k, passes = std::max(1, (m + kMaxRowsPerPass - 1) / kMaxRowsPerPass);
+  for (size_t r = 0; r < plan.rounds.size() && !rc; r++) {
+    const UpdateRound &rd = plan.rounds[r];
+    for (int p = 0; p < passes && !rc; p++) {
+      const int row0 = p * kMaxRowsPerPass, rows = std::min(kMaxRowsPerPass, m - row0);
+      const uint8_t *coef = parity + static_cast<size_t>(row0) * k;
+      const bool last = p == passes - 1;
+      rc = launch_update_vec(k, rows, row0, coef, d_stripes, chunk_stride, d_items, d_tiles + rd.tile0, rd.ntiles, last,
+                             rd.nupdates, static_cast<int>(r), p, ctx->num_cus, st);
+      if (!rc)
+        rc = launch_update_bytes(k, rows, row0, coef, d_stripes, chunk_stride, d_items + rd.byte_item0,
+                                 d_prefix + rd.prefix0, rd.nbyte_items, rd.nbytes, last, static_cast<int>(r), p,
+                                 ctx->num_cus, st);
+    }
+  }
+  kt_end(ctx, kt, st);
+  // the tables stay in the slot until the stream gets past the launches
+  if (!rc) rc = hip_check(hipEventRecord(slot->busy, st), "slot event record");
+  slot->busy_set = !rc;
+  if (rc) (void)hipStreamSynchronize(st);
+  release_slot(ctx, slot);
+  return rc;
+}
+
 int nxec_rs_scrub_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripes, int64_t chunk_stride,
                           int64_t stripe_stride, int64_t len, int64_t nstripes, int flags, int32_t *d_status,
                           unsigned long long *d_nbad, void *stream) {

@@ -122,6 +122,30 @@ def rs_recover_mixed_plan(n: int, k: int, alive):
     return res, npat.value, nseg.value, ncoded.value
 
 
+def _update_list(updates):
+    """A ctypes array of nxec_update from (stripe, chunk, offset, length, d_new_ptr) tuples (None when empty)."""
+    ups = list(updates)
+    if not ups:
+        return None, 0
+    arr = (_lib.Update * len(ups))()
+    for u, (stripe, chunk, offset, length, d_new) in zip(arr, ups):
+        u.stripe, u.chunk, u.reserved, u.offset, u.length = int(stripe), int(chunk), 0, int(offset), int(length)
+        u.d_new = int(d_new) if d_new else None
+    return arr, len(ups)
+
+
+def rs_update_plan(n: int, k: int, chunk_stride: int, stripe_stride: int, length: int, nstripes: int,
+                   stripes_addr: int, updates):
+    """nxec_rs_update_plan, the host half of Context.rs_update (no device): `updates` is a sequence of
+    (stripe, chunk, offset, length, d_new_ptr), `stripes_addr` the batch's device address.  Returns
+    (rounds, vector tiles, byte items)."""
+    arr, nu = _update_list(updates)
+    nr, nt, nb = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib.nxec_rs_update_plan(n, k, chunk_stride, stripe_stride, length, nstripes, int(stripes_addr), arr, nu,
+                                  C.byref(nr), C.byref(nt), C.byref(nb)), "nxec_rs_update_plan")
+    return nr.value, nt.value, nb.value
+
+
 LAYOUT_RECOVER_HEAVY = 1
 OBJECTS_TAIL_INPLACE = 1  # nxec_encode_objects_ex: only the partial last-stripe chunk to the tail arena
 OBJECTS_ASYNC = 2  # nxec_encode_objects_ex: return once queued on the stream
@@ -547,6 +571,16 @@ class Context:
                                                 chunk_stride, stripe_stride, length, nstripes,
                                                 C.c_void_p(res.ctypes.data), stream), "nxec_rs_recover_stripes_mixed")
         return res
+
+    def rs_update(self, n: int, k: int, stripes: int, chunk_stride: int, stripe_stride: int, length: int,
+                  nstripes: int, updates, stream=None) -> None:
+        """nxec_rs_update_stripes: overwrite byte ranges of data chunks and bring the parity along by
+        c(r,j) * (new ^ old).  `updates` is a sequence of (stripe, chunk, offset, length, d_new_ptr) with the
+        new bytes in device memory outside the batch.  Asynchronous on `stream`; the new bytes must stay
+        valid until the stream gets there."""
+        arr, nu = _update_list(updates)
+        check(lib.nxec_rs_update_stripes(C.c_void_p(self.ptr), n, k, C.c_void_p(int(stripes)), chunk_stride,
+                                         stripe_stride, length, nstripes, arr, nu, stream), "nxec_rs_update_stripes")
 
     def rs_scrub_stripes(self, n: int, k: int, stripes: int, chunk_stride: int, stripe_stride: int, length: int,
                          nstripes: int, status: int, flags: int = 0, nbad=None, stream=None) -> None:
