@@ -277,6 +277,69 @@ int nxec_rs_recover_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned 
 int nxec_rs_recover_mixed_plan(int n, int k, const unsigned char *alive, int64_t nstripes, int32_t *result,
                                int64_t *npatterns, int64_t *nsegments, int64_t *ncoded);
 
+/* Mixed-pattern decode: the read path for a batch whose stripes lost different
+ * chunks (a container down, a digest that did not match, a fetch that timed
+ * out).  alive (HOST, [nstripes][n]) is the map of the mixed recover: any
+ * non-zero byte means the chunk is present and trusted, so a downloaded d_ok
+ * of nxec_md5_verify_chunks / nxec_decode_object_verify is a valid alive map.
+ * Caveat: chunks that verify did not read keep the d_ok value the caller
+ * preset, so they are trusted as preset; a caller who wants all n chunks
+ * checked runs nxec_md5_verify_chunks over all of them first.
+ *
+ * Per stripe, with E the ascending erased ids and T the data ids in E (< k):
+ *   |E| > n-k         no byte of the stripe is read, no byte of its output
+ *                     written, result NXEC_RECOVER_LOST;
+ *   T not empty and the first k alive chunks do not invert (exactly when
+ *   nxec_rs_decode_stripes with failed = E returns NXEC_ERR_SINGULAR)
+ *                     untouched as above, result NXEC_RECOVER_SINGULAR;
+ *   otherwise         all k data chunks are written, chunk j of stripe s to
+ *                     d_out + s*out_stripe_stride + j*out_chunk_stride,
+ *                     result |T|: byte for byte what
+ *                     nxec_rs_decode_stripes(ctx, n, k, E, |E|, ...) writes
+ *                     for that stripe alone.  The inputs are the first k alive
+ *                     chunks (rs.cc:252-265); lost data chunks go through the
+ *                     inverse rows, surviving ones are copied.  A clean stripe
+ *                     or one that lost only parity gives 0: k copies, no table
+ *                     lookup.
+ * Erased slots of d_stripes are never read, d_stripes is never written, bytes
+ * between output chunks (stride padding) are never written.
+ *
+ * alive is read and result (HOST, [nstripes], may be NULL) written before the
+ * call returns; both may be reused at once.  The device work is asynchronous
+ * on `stream` with no host synchronisation inside; the device tables are
+ * staged in a context slot released with an event, as the mixed recover stages
+ * its own.  The call returns NXEC_OK when some stripes are LOST or SINGULAR:
+ * the verdicts are in result.
+ *
+ * Two paths, shown by the launch record (nxec_debug_launch_log):
+ *   one launch  k <= 19, both bases and all four strides 16-byte aligned and
+ *               len % 16 == 0: one plan per distinct input set (the first k
+ *               alive ids; stripes that differ only in erased chunks beyond
+ *               their k-th alive one share it), and one queue-driven kernel
+ *               (k_decode_mixed) over every decoded stripe;
+ *   by runs     every other shape: one nxec_rs_decode_stripes per maximal run
+ *               of consecutive stripes with an equal plan, clean runs included.
+ *
+ * NULL ctx, invalid (n,k), negative len, nstripes or strides, NULL alive with
+ * nstripes > 0, NULL buffers when there is work to do, source or output chunk
+ * offsets of a stripe beyond 4 GiB, out_chunk_stride < len, out_stripe_stride
+ * too small for k chunks, or an output range that intersects the source range
+ * [d_stripes, d_stripes + nstripes*stripe_stride) (the kernel loads the next
+ * tile before it stores the current one) give NXEC_ERR_INVALID before any
+ * device use (result is then not written).  len == 0 or nstripes == 0 launches
+ * nothing; result is still filled. */
+int nxec_rs_decode_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned char *alive,
+                                 const unsigned char *d_stripes, int64_t chunk_stride, int64_t stripe_stride,
+                                 unsigned char *d_out, int64_t out_chunk_stride, int64_t out_stripe_stride,
+                                 int64_t len, int64_t nstripes, int32_t *result, void *stream);
+/* The host half alone (pure, no device): result as above (may be NULL);
+ * *nplans = distinct decode plans, keyed by the input set (the clean plan,
+ * inputs 0..k-1, counts when any stripe uses it), *nsegments = the sum over
+ * the plans of max(1, ceil(|T| / 4)), *ndecoded = stripes with result >= 0
+ * (each may be NULL). */
+int nxec_rs_decode_mixed_plan(int n, int k, const unsigned char *alive, int64_t nstripes, int32_t *result,
+                              int64_t *nplans, int64_t *nsegments, int64_t *ndecoded);
+
 /* Delta update: overwrite byte ranges of data chunks of coded stripes and
  * bring the parity along, without reading the other data chunks.  The code is
  * linear, so for an update of data chunk j of a stripe over the byte columns
@@ -594,12 +657,30 @@ int nxec_decode_object_ex(nxec_ctx_t *ctx, int n, int k, const int32_t *failed, 
  * max_chunk_size is a multiple of 256).  d_ok [ns][n]: byte (s, c) = 1 if
  * chunk c of stripe s matched, 0 if not; entries of chunks that were not read
  * are left as they were.  *d_nbad (device, optional, not reset) += mismatches.
- * A stripe with a mismatch decodes to undefined bytes: re-plan it with the
- * bad chunks marked failed (the reference fails such a stripe's read). */
+ * A stripe with a mismatch decodes to undefined bytes: download d_ok and pass
+ * it as the alive map of nxec_decode_object_mixed, which decodes every stripe
+ * around its own bad chunks in one call (the reference fails such a stripe's
+ * read). */
 int nxec_decode_object_verify(nxec_ctx_t *ctx, int n, int k, const int32_t *failed, int nfailed,
                               const unsigned char *d_chunks, int64_t length, int64_t max_chunk_size,
                               const unsigned char *d_md5, unsigned char *d_object, unsigned char *d_tail,
                               unsigned char *d_ok, unsigned long long *d_nbad, void *stream);
+
+/* nxec_decode_object_ex with a per-stripe map: alive (HOST) and result (HOST,
+ * may be NULL) have one row / entry per stripe of the object, with the
+ * semantics of nxec_rs_decode_stripes_mixed.  Full stripes go through the
+ * mixed decode straight into the object (out_chunk_stride = M,
+ * out_stripe_stride = k*M); the last stripe is decoded with its own erased
+ * list through nxec_rs_decode_stripes into d_tail and its unpadded bytes are
+ * copied.  A LOST or SINGULAR stripe, the last one included, is skipped (its
+ * object bytes are not written) and reported in result; the call still returns
+ * NXEC_OK.  Caveat, as above: chunks that nxec_decode_object_verify did not
+ * read are trusted as d_ok was preset; run nxec_md5_verify_chunks over all n
+ * chunks first to have every chunk checked. */
+int nxec_decode_object_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned char *alive,
+                             const unsigned char *d_chunks, int64_t chunk_stride, int64_t stripe_stride,
+                             int64_t length, int64_t max_chunk_size, unsigned char *d_object,
+                             unsigned char *d_tail, int32_t *result, void *stream);
 
 /* Many objects in one call (the proxy's per-file loop, proxy_file_ops.cc:557-666,
  * over a batch of files): object o (d_objects[o], a HOST array of device

@@ -63,6 +63,10 @@ _PROTOS = {
     "nxec_rs_recover_stripes_mixed": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, i64, i64, i64, i64, vp, vp]),
     "nxec_rs_recover_mixed_plan": (C.c_int, [C.c_int, C.c_int, vp, i64, vp, C.POINTER(i64), C.POINTER(i64),
                                              C.POINTER(i64)]),
+    "nxec_rs_decode_stripes_mixed": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, i64, i64, vp, i64, i64, i64, i64, vp, vp]),
+    "nxec_rs_decode_mixed_plan": (C.c_int, [C.c_int, C.c_int, vp, i64, vp, C.POINTER(i64), C.POINTER(i64),
+                                            C.POINTER(i64)]),
+    "nxec_decode_object_mixed": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp]),
     "nxec_rs_update_stripes": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, i64, i64, i64, vp, i64, vp]),
     "nxec_rs_update_plan": (C.c_int, [C.c_int, C.c_int, i64, i64, i64, i64, C.c_size_t, vp, i64, C.POINTER(i64),
                                       C.POINTER(i64), C.POINTER(i64)]),

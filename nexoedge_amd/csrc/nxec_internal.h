@@ -244,6 +244,60 @@ const void *mixed_kernel(int k, int *lds_bytes);
 int launch_mul_mixed(int k, uint8_t *base, int64_t stripe_stride, int64_t len, const MixedSeg *d_segs,
                      const uint32_t *d_order, const uint32_t *d_seg_of, int64_t nitems, int64_t nsegs, int64_t ncoded,
                      int num_cus, void *stream);
+// Mixed-pattern decode (nxec_rs_decode_stripes_mixed): the full-output form of
+// the mixed recover.  Every stripe of the batch names its own erased chunks and
+// all k data chunks of every decodable stripe go to a separate output.  Host
+// half (nxec_decode_mixed_host.cpp, pure arithmetic, no device).  A decode plan
+// is keyed by its input set, the first k alive ids: the erased data chunks are
+// exactly the data ids missing from it, so stripes that differ only in erased
+// chunks beyond their k-th alive one share a plan.
+struct DecodePlan {
+  struct Plan {
+    std::vector<int32_t> inputs;   // the first k alive ids, ascending
+    std::vector<int32_t> targets;  // T: the erased data ids (ids < k not among the inputs), ascending
+    std::vector<int32_t> erased;   // every id below inputs[k-1] that is no input: the shortest `failed`
+                                   // list with which nxec_rs_decode_stripes makes this plan (by-runs path)
+    std::vector<uint8_t> rows;     // |T| x k rows of nxec_rs_decode_matrix
+  };
+  std::vector<Plan> plans;       // in order of first appearance
+  std::vector<int32_t> plan_of;  // per stripe: index into plans, -1 for a LOST or SINGULAR stripe
+  int64_t nsegments = 0;         // sum over the plans of max(1, ceil(|T| / kMaxRowsPerPass))
+  int64_t ndecoded = 0;          // stripes with result >= 0
+};
+// result[s] (nstripes entries, may be NULL) as nxec_rs_decode_stripes_mixed
+// documents it; arguments are validated by the caller.
+void decode_mixed_plan(int n, int k, const uint8_t *alive, int64_t nstripes, int32_t *result, DecodePlan *plan);
+// One segment of a decode plan as the kernel reads it: MixedSeg plus the
+// pass-through of surviving data chunks.  copy_off[j] is the output offset of
+// source j where that source is a data chunk, else kNoCopy; only the first
+// segment of a plan copies.  src_off are offsets inside a source stripe,
+// dst_off and copy_off inside an output stripe.  rows may be 0 (a plan with no
+// lost data chunk: k copies, no table lookup); coefficient rows >= rows are zero.
+struct DecodeSeg {
+  uint32_t rows;
+  uint32_t dst_off[kMaxRowsPerPass];
+  uint32_t src_off[kMaxRaggedK];
+  uint32_t copy_off[kMaxRaggedK];
+  uint8_t coef[kMaxRowsPerPass * kMaxRaggedK];  // row-major rows x k
+  uint8_t pad[8];
+};
+static_assert(sizeof(DecodeSeg) % 16 == 0, "segment records are staged 16-byte aligned");
+// The device tables of a decode plan (k <= kMaxDecodeMixedK, source and output
+// chunk offsets below 4 GiB), like mixed_tables: items run by segment, then
+// ascending stripe; a stripe with more than 4 lost data chunks appears once per
+// segment of its plan.
+void decode_mixed_tables(const DecodePlan &plan, int k, int64_t chunk_stride, int64_t out_chunk_stride,
+                         std::vector<DecodeSeg> &segs, std::vector<uint32_t> &order, std::vector<uint32_t> &seg_of);
+// The widest k with a k_decode_mixed instantiation; wider k take the by-runs path.
+constexpr int kMaxDecodeMixedK = kMaxRaggedK;
+// The decode kernel of k <= kMaxDecodeMixedK and the dynamic LDS its launch asks for.
+const void *decode_mixed_kernel(int k, int *lds_bytes);
+// One launch over nitems items of len bytes per chunk (a multiple of 16; both
+// bases, all four strides and every offset 16-byte aligned); tables in device
+// memory.  nsegs / ndecoded only go to the launch record.
+int launch_decode_mixed(int k, const uint8_t *src, int64_t stripe_stride, uint8_t *dst, int64_t out_stripe_stride,
+                        int64_t len, const DecodeSeg *d_segs, const uint32_t *d_order, const uint32_t *d_seg_of,
+                        int64_t nitems, int64_t nsegs, int64_t ndecoded, int num_cus, void *stream);
 // Delta update (nxec_rs_update_stripes): byte ranges of data chunks are
 // overwritten and the parity follows by c(r,j) (x) (new ^ old).  Host half
 // (nxec_update_host.cpp, pure arithmetic, no device): validation, the rounds,

@@ -480,6 +480,51 @@ int nxec_decode_object_ex(nxec_ctx_t *ctx, int n, int k, const int32_t *failed, 
   return hip_check(hipMemcpyAsync(d_object + nf * k * M, d_tail, rem, hipMemcpyDeviceToDevice, st), "tail copy");
 }
 
+int nxec_decode_object_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned char *alive,
+                             const unsigned char *d_chunks, int64_t chunk_stride, int64_t stripe_stride,
+                             int64_t length, int64_t max_chunk_size, unsigned char *d_object,
+                             unsigned char *d_tail, int32_t *result, void *stream) {
+  if (!ctx) return set_error(NXEC_ERR_INVALID, "null context");
+  int64_t ns = 0, nf = 0, cs_last = 0;
+  int rc = nxec_object_layout(n, k, length, max_chunk_size, &ns, &nf, &cs_last);
+  if (rc) return rc;
+  if (ns == 0) return NXEC_OK;
+  const int64_t M = max_chunk_size;
+  const bool tail = ns > nf;
+  if (!alive) return set_error(NXEC_ERR_INVALID, "nxec_decode_object_mixed: null alive map");
+  if (!d_chunks || !d_object || (tail && !d_tail))
+    return set_error(NXEC_ERR_INVALID, "nxec_decode_object_mixed: null buffer");
+  if (chunk_stride < M || stripe_stride < int64_t(n) * chunk_stride)
+    return set_error(NXEC_ERR_INVALID, "nxec_decode_object_mixed: strides smaller than the chunks");
+  std::vector<int32_t> verdict(static_cast<size_t>(ns));
+  // full stripes straight into the object: data chunk j of stripe s at s*k*M + j*M
+  if (nf > 0) {
+    rc = nxec_rs_decode_stripes_mixed(ctx, n, k, alive, d_chunks, chunk_stride, stripe_stride, d_object, M, k * M, M, nf,
+                                      verdict.data(), stream);
+    if (rc) return rc;
+  }
+  if (tail) {
+    // last stripe: chunks of cs_last bytes in the same slots, decoded with its own erased list to scratch;
+    // the unpadded bytes are kept.  A LOST or SINGULAR last stripe is skipped and reported.
+    const unsigned char *a = alive + nf * n;
+    std::vector<int32_t> erased;
+    for (int c = 0; c < n; c++)
+      if (!a[c]) erased.push_back(c);
+    decode_mixed_plan(n, k, a, 1, &verdict[static_cast<size_t>(nf)], nullptr);
+    if (verdict[static_cast<size_t>(nf)] >= 0) {
+      hipStream_t st = pick_stream(ctx, stream);
+      rc = nxec_rs_decode_stripes(ctx, n, k, erased.data(), static_cast<int>(erased.size()), d_chunks + nf * stripe_stride,
+                                  chunk_stride, stripe_stride, d_tail, cs_last, k * cs_last, cs_last, 1, st);
+      if (rc) return rc;
+      const int64_t rem = length - nf * k * M;
+      rc = hip_check(hipMemcpyAsync(d_object + nf * k * M, d_tail, rem, hipMemcpyDeviceToDevice, st), "tail copy");
+      if (rc) return rc;
+    }
+  }
+  if (result) std::memcpy(result, verdict.data(), verdict.size() * sizeof(int32_t));
+  return NXEC_OK;
+}
+
 int nxec_decode_object_verify(nxec_ctx_t *ctx, int n, int k, const int32_t *failed, int nfailed,
                               const unsigned char *d_chunks, int64_t length, int64_t max_chunk_size,
                               const unsigned char *d_md5, unsigned char *d_object, unsigned char *d_tail,

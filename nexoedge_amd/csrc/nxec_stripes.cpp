@@ -142,6 +142,44 @@ static int scrub_coef(int device, int n, int k, const uint8_t *rows, const uint8
   return NXEC_OK;
 }
 
+// The device tables of a mixed launch (segment records, then order[], then
+// seg_of[], each 16-byte aligned) staged in a context slot that the stream
+// releases with an event: no host synchronisation on the caller's stream.
+// launch(d_segs, d_order, d_seg_of, count) enqueues `count` items; d_order and
+// d_seg_of already point at the first of them (a batch of more tiles than one
+// launch holds goes out in several).
+template <class Seg, class LaunchF>
+int staged_mixed_launch(nxec_ctx_t *ctx, const std::vector<Seg> &segs, const std::vector<uint32_t> &order,
+                               const std::vector<uint32_t> &seg_of, int64_t len, hipStream_t st, const LaunchF &launch) {
+  const size_t seg_bytes = segs.size() * sizeof(Seg);
+  const size_t item_bytes = (order.size() * sizeof(uint32_t) + 15) / 16 * 16;
+  Slot *slot = nullptr;
+  int rc = acquire_slot(ctx, seg_bytes + 2 * item_bytes, &slot, true);
+  if (rc) return rc;
+  // the slot's staging may still be in use by an earlier call on its own stream
+  rc = hip_check(hipStreamSynchronize(slot->stream), "slot sync");
+  if (!rc && !slot->busy) rc = hip_check(hipEventCreateWithFlags(&slot->busy, hipEventDisableTiming), "slot event");
+  if (!rc) {
+    std::memcpy(slot->h, segs.data(), seg_bytes);
+    std::memcpy(slot->h + seg_bytes, order.data(), order.size() * sizeof(uint32_t));
+    std::memcpy(slot->h + seg_bytes + item_bytes, seg_of.data(), seg_of.size() * sizeof(uint32_t));
+    rc = hip_check(hipMemcpyAsync(slot->d, slot->h, seg_bytes + 2 * item_bytes, hipMemcpyHostToDevice, st), "tables H2D");
+  }
+  hipEvent_t kt[2];
+  kt_begin(ctx, st, kt);
+  const int64_t per = max_stripes_per_launch(len / 16), nitems = static_cast<int64_t>(order.size());
+  for (int64_t i0 = 0; i0 < nitems && !rc; i0 += per)
+    rc = launch(reinterpret_cast<const Seg *>(slot->d), reinterpret_cast<const uint32_t *>(slot->d + seg_bytes) + i0,
+                reinterpret_cast<const uint32_t *>(slot->d + seg_bytes + item_bytes) + i0, std::min(per, nitems - i0));
+  kt_end(ctx, kt, st);
+  // the tables stay in the slot until the stream gets past the launches
+  if (!rc) rc = hip_check(hipEventRecord(slot->busy, st), "slot event record");
+  slot->busy_set = !rc;
+  if (rc) (void)hipStreamSynchronize(st);
+  release_slot(ctx, slot);
+  return rc;
+}
+
 }  // namespace nxec
 
 using namespace nxec;
@@ -225,42 +263,17 @@ static int recover_mixed_by_runs(nxec_ctx_t *ctx, int n, int k, const MixedPlan 
   return NXEC_OK;
 }
 
-// One-launch path: the plan's tables staged in a context slot that the stream
-// releases with an event (no host synchronisation on the caller's stream).
+// One-launch path of the mixed recover.
 static int recover_mixed_one_launch(nxec_ctx_t *ctx, int k, const MixedPlan &plan, unsigned char *d_stripes,
                                     int64_t cs, int64_t ss, int64_t len, hipStream_t st) {
   std::vector<MixedSeg> segs;
   std::vector<uint32_t> order, seg_of;
   mixed_tables(plan, k, cs, segs, order, seg_of);
-  const size_t seg_bytes = segs.size() * sizeof(MixedSeg);
-  const size_t item_bytes = (order.size() * sizeof(uint32_t) + 15) / 16 * 16;
-  Slot *slot = nullptr;
-  int rc = acquire_slot(ctx, seg_bytes + 2 * item_bytes, &slot, true);
-  if (rc) return rc;
-  // the slot's staging may still be in use by an earlier call on its own stream
-  rc = hip_check(hipStreamSynchronize(slot->stream), "slot sync");
-  if (!rc && !slot->busy) rc = hip_check(hipEventCreateWithFlags(&slot->busy, hipEventDisableTiming), "slot event");
-  if (!rc) {
-    std::memcpy(slot->h, segs.data(), seg_bytes);
-    std::memcpy(slot->h + seg_bytes, order.data(), order.size() * sizeof(uint32_t));
-    std::memcpy(slot->h + seg_bytes + item_bytes, seg_of.data(), seg_of.size() * sizeof(uint32_t));
-    rc = hip_check(hipMemcpyAsync(slot->d, slot->h, seg_bytes + 2 * item_bytes, hipMemcpyHostToDevice, st), "tables H2D");
-  }
-  hipEvent_t kt[2];
-  kt_begin(ctx, st, kt);
-  const int64_t per = max_stripes_per_launch(len / 16), nitems = static_cast<int64_t>(order.size());
-  for (int64_t i0 = 0; i0 < nitems && !rc; i0 += per)
-    rc = launch_mul_mixed(k, d_stripes, ss, len, reinterpret_cast<const MixedSeg *>(slot->d),
-                          reinterpret_cast<const uint32_t *>(slot->d + seg_bytes) + i0,
-                          reinterpret_cast<const uint32_t *>(slot->d + seg_bytes + item_bytes) + i0,
-                          std::min(per, nitems - i0), static_cast<int64_t>(segs.size()), plan.ncoded, ctx->num_cus, st);
-  kt_end(ctx, kt, st);
-  // the tables stay in the slot until the stream gets past the launches
-  if (!rc) rc = hip_check(hipEventRecord(slot->busy, st), "slot event record");
-  slot->busy_set = !rc;
-  if (rc) (void)hipStreamSynchronize(st);
-  release_slot(ctx, slot);
-  return rc;
+  return staged_mixed_launch(ctx, segs, order, seg_of, len, st,
+                             [&](const MixedSeg *d_segs, const uint32_t *d_order, const uint32_t *d_seg_of, int64_t count) {
+                               return launch_mul_mixed(k, d_stripes, ss, len, d_segs, d_order, d_seg_of, count,
+                                                       static_cast<int64_t>(segs.size()), plan.ncoded, ctx->num_cus, st);
+                             });
 }
 
 int nxec_rs_recover_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned char *alive,
@@ -303,7 +316,7 @@ int nxec_rs_recover_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned 
 }
 
 // Delta update: the planner's tables staged in a context slot that the stream
-// releases with an event (recover_mixed_one_launch's scheme), then per round
+// releases with an event (staged_mixed_launch's scheme), then per round
 // and per pass of <= 4 parity rows the vector launch and the byte launch.
 int nxec_rs_update_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripes, int64_t chunk_stride,
                            int64_t stripe_stride, int64_t len, int64_t nstripes, const nxec_update *updates,
@@ -466,6 +479,98 @@ int nxec_rs_decode_stripes(nxec_ctx_t *ctx, int n, int k, const int32_t *failed,
   return stripes_mul_impl(ctx, static_cast<int>(targets.size()), k, m.data(), d_stripes, nullptr, inputs.data(),
                           chunk_stride, stripe_stride, d_out, nullptr, targets.data(), out_chunk_stride,
                           out_stripe_stride, copy.data(), len, nstripes, stream);
+}
+
+// By-runs path of the mixed decode: one nxec_rs_decode_stripes per maximal run
+// of consecutive stripes with an equal plan, clean runs included (any k,
+// alignment and length).  The plan's `erased` list makes exactly its inputs.
+static int decode_mixed_by_runs(nxec_ctx_t *ctx, int n, int k, const DecodePlan &plan, const unsigned char *d_stripes,
+                                int64_t cs, int64_t ss, unsigned char *d_out, int64_t ocs, int64_t oss, int64_t len,
+                                int64_t nstripes, void *stream) {
+  for (int64_t s0 = 0; s0 < nstripes;) {
+    const int32_t pi = plan.plan_of[s0];
+    int64_t s1 = s0 + 1;
+    while (s1 < nstripes && plan.plan_of[s1] == pi) s1++;
+    if (pi >= 0) {
+      const std::vector<int32_t> &e = plan.plans[pi].erased;
+      if (int rc = nxec_rs_decode_stripes(ctx, n, k, e.data(), static_cast<int>(e.size()), d_stripes + s0 * ss, cs, ss,
+                                          d_out + s0 * oss, ocs, oss, len, s1 - s0, stream))
+        return rc;
+    }
+    s0 = s1;
+  }
+  return NXEC_OK;
+}
+
+// One-launch path of the mixed decode: tables staged exactly as the mixed recover's.
+static int decode_mixed_one_launch(nxec_ctx_t *ctx, int k, const DecodePlan &plan, const unsigned char *d_stripes,
+                                   int64_t cs, int64_t ss, unsigned char *d_out, int64_t ocs, int64_t oss, int64_t len,
+                                   hipStream_t st) {
+  std::vector<DecodeSeg> segs;
+  std::vector<uint32_t> order, seg_of;
+  decode_mixed_tables(plan, k, cs, ocs, segs, order, seg_of);
+  return staged_mixed_launch(ctx, segs, order, seg_of, len, st,
+                             [&](const DecodeSeg *d_segs, const uint32_t *d_order, const uint32_t *d_seg_of, int64_t count) {
+                               return launch_decode_mixed(k, d_stripes, ss, d_out, oss, len, d_segs, d_order, d_seg_of, count,
+                                                          static_cast<int64_t>(segs.size()), plan.ndecoded, ctx->num_cus, st);
+                             });
+}
+
+int nxec_rs_decode_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned char *alive,
+                                 const unsigned char *d_stripes, int64_t chunk_stride, int64_t stripe_stride,
+                                 unsigned char *d_out, int64_t out_chunk_stride, int64_t out_stripe_stride,
+                                 int64_t len, int64_t nstripes, int32_t *result, void *stream) {
+  if (!ctx) return set_error(NXEC_ERR_INVALID, "null context");
+  if (!valid_nk(n, k)) return set_error(NXEC_ERR_INVALID, "invalid (n,k)=(%d,%d)", n, k);
+  if (len < 0 || nstripes < 0) return set_error(NXEC_ERR_INVALID, "negative len or nstripes");
+  if (chunk_stride < 0 || stripe_stride < 0) return set_error(NXEC_ERR_INVALID, "mixed decode: negative source stride");
+  if (!alive && nstripes > 0) return set_error(NXEC_ERR_INVALID, "mixed decode: null alive map");
+  if (out_chunk_stride < len || out_stripe_stride < static_cast<__int128>(k - 1) * out_chunk_stride + len)
+    return set_error(NXEC_ERR_INVALID, "mixed decode: output strides smaller than the chunks");
+  // chunk byte offsets inside a stripe stay 32-bit (the kernels' scalar address math)
+  constexpr int64_t kOffMax = (int64_t(1) << 32) - 1;
+  if (len > 0 && nstripes > 0 &&
+      (chunk_stride > kOffMax || out_chunk_stride > kOffMax || static_cast<int64_t>(n - 1) * chunk_stride + len > kOffMax ||
+       static_cast<int64_t>(k - 1) * out_chunk_stride + len > kOffMax))
+    return set_error(NXEC_ERR_INVALID, "mixed decode: chunk offset out of range (chunks of a stripe must lie within 4 GiB)");
+  // the output must stay clear of the source: the kernel loads tile t+1 before it stores tile t
+  if (len > 0 && nstripes > 0 && d_stripes && d_out) {
+    const __int128 src0 = reinterpret_cast<uintptr_t>(d_stripes), dst0 = reinterpret_cast<uintptr_t>(d_out);
+    const __int128 src1 = src0 + static_cast<__int128>(nstripes) * stripe_stride;
+    const __int128 dst1 = dst0 + static_cast<__int128>(nstripes - 1) * out_stripe_stride +
+                          static_cast<__int128>(k - 1) * out_chunk_stride + len;
+    if (dst0 < src1 && src0 < dst1) return set_error(NXEC_ERR_INVALID, "mixed decode: the output intersects the source");
+  }
+  // stripe ids are 32-bit in the device tables: larger batches go block by block
+  constexpr int64_t kBlockStripes = int64_t(1) << 31;
+  if (nstripes > kBlockStripes) {
+    for (int64_t s0 = 0; s0 < nstripes; s0 += kBlockStripes)
+      if (int rc = nxec_rs_decode_stripes_mixed(ctx, n, k, alive + s0 * n, d_stripes ? d_stripes + s0 * stripe_stride : nullptr,
+                                                chunk_stride, stripe_stride, d_out ? d_out + s0 * out_stripe_stride : nullptr,
+                                                out_chunk_stride, out_stripe_stride, len,
+                                                std::min(kBlockStripes, nstripes - s0), result ? result + s0 : nullptr,
+                                                stream))
+        return rc;
+    return NXEC_OK;
+  }
+  std::vector<int32_t> verdict(static_cast<size_t>(nstripes));
+  DecodePlan plan;
+  decode_mixed_plan(n, k, alive, nstripes, verdict.data(), &plan);
+  const bool work = plan.ndecoded > 0 && len > 0;
+  if (work && (!d_stripes || !d_out)) return set_error(NXEC_ERR_INVALID, "null stripe buffer");
+  int rc = NXEC_OK;
+  if (work) {
+    if ((rc = ensure_device(ctx->device))) return rc;
+    const bool one_launch = k <= kMaxDecodeMixedK && aligned16(d_stripes) && aligned16(d_out) && chunk_stride % 16 == 0 &&
+                            stripe_stride % 16 == 0 && out_chunk_stride % 16 == 0 && out_stripe_stride % 16 == 0 &&
+                            len % 16 == 0;
+    rc = one_launch ? decode_mixed_one_launch(ctx, k, plan, d_stripes, chunk_stride, stripe_stride, d_out,
+                                              out_chunk_stride, out_stripe_stride, len, pick_stream(ctx, stream))
+                    : decode_mixed_by_runs(ctx, n, k, plan, d_stripes, chunk_stride, stripe_stride, d_out,
+                                           out_chunk_stride, out_stripe_stride, len, nstripes, stream);
+  }
+  if (result && nstripes > 0) std::memcpy(result, verdict.data(), verdict.size() * sizeof(int32_t));
+  return rc;
 }
 
 int nxec_rs_car_repair_stripes(nxec_ctx_t *ctx, int n, int k, int failed, const int32_t *group_offsets,

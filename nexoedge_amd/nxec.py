@@ -122,6 +122,20 @@ def rs_recover_mixed_plan(n: int, k: int, alive):
     return res, npat.value, nseg.value, ncoded.value
 
 
+def rs_decode_mixed_plan(n: int, k: int, alive):
+    """nxec_rs_decode_mixed_plan, the host half of Context.rs_decode_mixed (no device): `alive` is
+    [nstripes][n], non-zero = chunk present and trusted.  Returns (int32 result per stripe: lost data chunks
+    that go through inverse rows, RECOVER_LOST or RECOVER_SINGULAR; distinct decode plans, keyed by the first
+    k alive ids; segments; decoded stripes)."""
+    a = _alive_map(n, alive)
+    ns = a.size // n if n > 0 else 0
+    res = np.zeros(ns, dtype=np.int32)
+    nplans, nseg, ndec = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib.nxec_rs_decode_mixed_plan(n, k, _u8(a), ns, C.c_void_p(res.ctypes.data), C.byref(nplans), C.byref(nseg),
+                                        C.byref(ndec)), "nxec_rs_decode_mixed_plan")
+    return res, nplans.value, nseg.value, ndec.value
+
+
 def _update_list(updates):
     """A ctypes array of nxec_update from (stripe, chunk, offset, length, d_new_ptr) tuples (None when empty)."""
     ups = list(updates)
@@ -572,6 +586,23 @@ class Context:
                                                 C.c_void_p(res.ctypes.data), stream), "nxec_rs_recover_stripes_mixed")
         return res
 
+    def rs_decode_mixed(self, n: int, k: int, alive, stripes: int, chunk_stride: int, stripe_stride: int, out: int,
+                        out_chunk_stride: int, out_stripe_stride: int, length: int, nstripes: int,
+                        stream=None) -> np.ndarray:
+        """nxec_rs_decode_stripes_mixed: every stripe decodes around its own erased chunks (`alive`
+        [nstripes][n], 0 = erased) into `out`, which must not intersect the source.  Asynchronous on
+        `stream`; `alive` may be reused at once.  Returns the int32 result per stripe (see
+        rs_decode_mixed_plan)."""
+        a = _alive_map(n, alive)
+        if a.size != n * nstripes:
+            raise ValueError(f"alive map of {a.size} bytes for {nstripes} stripes of {n} chunks")
+        res = np.zeros(nstripes, dtype=np.int32)
+        check(lib.nxec_rs_decode_stripes_mixed(C.c_void_p(self.ptr), n, k, _u8(a), C.c_void_p(int(stripes)),
+                                               chunk_stride, stripe_stride, C.c_void_p(int(out)), out_chunk_stride,
+                                               out_stripe_stride, length, nstripes, C.c_void_p(res.ctypes.data),
+                                               stream), "nxec_rs_decode_stripes_mixed")
+        return res
+
     def rs_update(self, n: int, k: int, stripes: int, chunk_stride: int, stripe_stride: int, length: int,
                   nstripes: int, updates, stream=None) -> None:
         """nxec_rs_update_stripes: overwrite byte ranges of data chunks and bring the parity along by
@@ -706,6 +737,22 @@ class Context:
                                             C.c_void_p(int(tail) if tail else None), C.c_void_p(int(ok)),
                                             C.c_void_p(int(nbad) if nbad else None), stream),
               "nxec_decode_object_verify")
+
+    def decode_object_mixed(self, n: int, k: int, alive, chunks: int, chunk_stride: int, stripe_stride: int,
+                            length: int, max_chunk_size: int, obj: int, tail=None, stream=None) -> np.ndarray:
+        """nxec_decode_object_mixed: decode_object_ex with a per-stripe `alive` map ([stripes of the object][n],
+        e.g. the downloaded ok map of decode_object_verify).  Returns the int32 result per stripe; a LOST or
+        SINGULAR stripe is skipped and its object bytes are left as they were."""
+        a = _alive_map(n, alive)
+        ns = object_layout(n, k, length, max_chunk_size)[0]
+        if a.size != n * ns:
+            raise ValueError(f"alive map of {a.size} bytes for {ns} stripes of {n} chunks")
+        res = np.zeros(ns, dtype=np.int32)
+        check(lib.nxec_decode_object_mixed(C.c_void_p(self.ptr), n, k, _u8(a) if a.size else None,
+                                           C.c_void_p(int(chunks)), chunk_stride, stripe_stride, length, max_chunk_size,
+                                           C.c_void_p(int(obj)), C.c_void_p(int(tail) if tail else None),
+                                           C.c_void_p(res.ctypes.data), stream), "nxec_decode_object_mixed")
+        return res
 
     def agent_encode_batch(self, reqs, chunk_size: int, batch_bytes: int = 0) -> None:
         """nxec_agent_encode_batch: reqs = [(matrix (no x ni), inputs [ni arrays], outputs [no arrays],
