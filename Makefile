@@ -15,7 +15,7 @@ OBJDIR   := build/obj
 
 LIB_SRCS := $(CSRC)/gf_host.cpp $(CSRC)/nxec_context.cpp $(CSRC)/nxec_stripes.cpp $(CSRC)/nxec_objects.cpp \
             $(CSRC)/nxec_host_paths.cpp $(CSRC)/nxec_host_encode.cpp $(CSRC)/nxec_agent.cpp $(CSRC)/nxec_probes.cpp \
-            $(CSRC)/nxec_scrub_host.cpp $(CSRC)/nxec_recover_mixed_host.cpp $(CSRC)/nxec_decode_mixed_host.cpp $(CSRC)/nxec_update_host.cpp \
+            $(CSRC)/nxec_scrub_host.cpp $(CSRC)/nxec_mixed_host.cpp $(CSRC)/nxec_update_host.cpp \
             $(CSRC)/nxec_kernels.hip $(CSRC)/nxec_md5.hip $(CSRC)/nxec_encode_md5.hip $(CSRC)/nxec_encode_md5_ring.hip \
             $(CSRC)/nxec_files_md5.hip \
             $(CSRC)/nxec_group.cpp $(CSRC)/nxec_host_arena.cpp $(CSRC)/nxec_digest.cpp $(CSRC)/nxec_digest_place.cpp $(CSRC)/nxec_numa.cpp $(CSRC)/nxec_config.cpp \
@@ -25,8 +25,8 @@ HDRS     := include/nxec.h $(CSRC)/nxec_internal.h $(CSRC)/nxec_runtime.h $(CSRC
 
 all: $(LIBDIR)/libnxec.so oracle/liboracle.so build/rs_surface_test build/isal_compat_test build/chunk_manager_flow_test \
      build/stripe_batch_test build/chunk_replay_test build/dropin_pool_test build/scrub_host_test \
-     build/recover_mixed_plan_test build/recover_mixed_registry_test build/update_plan_test build/update_registry_test \
-     build/decode_mixed_plan_test build/decode_mixed_registry_test
+     build/recover_mixed_plan_test build/decode_mixed_plan_test build/mixed_registry_test build/update_plan_test \
+     build/update_registry_test
 
 # rs.cc's ISA-L call sequence compiled against include/nxec_isal_compat.h (plain C)
 build/isal_compat_test: tests/cpp/isal_compat_test.c include/nxec_isal_compat.h $(LIBDIR)/libnxec.so
@@ -74,37 +74,24 @@ build/scrub_host_test: tests/cpp/scrub_host_test.cc $(CSRC)/nxec_scrub_host.cpp 
 scrub-host-test: build/scrub_host_test
 	build/scrub_host_test
 
-# the mixed-pattern recover's host planner (nxec_rs_recover_mixed_plan) the same way: ASan + UBSan,
-# the planner source and gf_host.cpp, no device and no libnxec
-build/recover_mixed_plan_test: tests/cpp/recover_mixed_plan_test.cc $(CSRC)/nxec_recover_mixed_host.cpp $(CSRC)/gf_host.cpp $(HDRS)
+# the host planner of the mixed-pattern recover and decode (nxec_rs_recover_mixed_plan, nxec_rs_decode_mixed_plan)
+# and its device tables the same way, one program per mode: ASan + UBSan, the planner source and gf_host.cpp, no
+# device and no libnxec
+build/%_mixed_plan_test: tests/cpp/%_mixed_plan_test.cc $(CSRC)/nxec_mixed_host.cpp $(CSRC)/gf_host.cpp $(HDRS)
 	@mkdir -p build
 	g++ -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
-	    -Iinclude -I$(CSRC) tests/cpp/recover_mixed_plan_test.cc $(CSRC)/nxec_recover_mixed_host.cpp $(CSRC)/gf_host.cpp -o $@
+	    -Iinclude -I$(CSRC) $< $(CSRC)/nxec_mixed_host.cpp $(CSRC)/gf_host.cpp -o $@
 recover-mixed-plan-test: build/recover_mixed_plan_test
 	build/recover_mixed_plan_test
-
-# the kernel the mixed launch picks for every k against the per-device preparation list (no sanitizers, no device)
-build/recover_mixed_registry_test: tests/cpp/recover_mixed_registry_test.cc $(LIBDIR)/libnxec.so $(HDRS)
-	@mkdir -p build
-	g++ -std=c++17 -O2 -Wall -Iinclude -I$(CSRC) $< -L$(LIBDIR) -lnxec -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -lcrypto -o $@
-recover-mixed-registry-test: build/recover_mixed_registry_test
-	build/recover_mixed_registry_test
-
-# the mixed-pattern decode's host planner (nxec_rs_decode_mixed_plan) and its device tables the same way: ASan + UBSan,
-# the planner source and gf_host.cpp, no device and no libnxec
-build/decode_mixed_plan_test: tests/cpp/decode_mixed_plan_test.cc $(CSRC)/nxec_decode_mixed_host.cpp $(CSRC)/gf_host.cpp $(HDRS)
-	@mkdir -p build
-	g++ -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
-	    -Iinclude -I$(CSRC) tests/cpp/decode_mixed_plan_test.cc $(CSRC)/nxec_decode_mixed_host.cpp $(CSRC)/gf_host.cpp -o $@
 decode-mixed-plan-test: build/decode_mixed_plan_test
 	build/decode_mixed_plan_test
 
-# every k_decode_mixed instantiation against the per-device preparation list (no sanitizers, no device)
-build/decode_mixed_registry_test: tests/cpp/decode_mixed_registry_test.cc $(LIBDIR)/libnxec.so $(HDRS)
+# every k_mul_mixed and k_decode_mixed instantiation against the per-device preparation list (no sanitizers, no device)
+build/mixed_registry_test: tests/cpp/mixed_registry_test.cc $(LIBDIR)/libnxec.so $(HDRS)
 	@mkdir -p build
 	g++ -std=c++17 -O2 -Wall -Iinclude -I$(CSRC) $< -L$(LIBDIR) -lnxec -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -lcrypto -o $@
-decode-mixed-registry-test: build/decode_mixed_registry_test
-	build/decode_mixed_registry_test
+mixed-registry-test: build/mixed_registry_test
+	build/mixed_registry_test
 
 # the delta update's host planner (nxec_rs_update_plan) the same way: ASan + UBSan, the planner source and
 # gf_host.cpp, no device and no libnxec
@@ -198,5 +185,4 @@ clean:
 	rm -rf build $(LIBDIR)/libnxec.so oracle/liboracle.so
 
 .PHONY: all ref golden clean tune tools asan ubsan tsan sanitize scrub-host-test recover-mixed-plan-test \
-        recover-mixed-registry-test update-plan-test update-registry-test decode-mixed-plan-test \
-        decode-mixed-registry-test
+        decode-mixed-plan-test mixed-registry-test update-plan-test update-registry-test

@@ -202,78 +202,46 @@ constexpr int kMaxRaggedK = 19;
 const void *ragged_kernel(int k, int *lds_bytes);
 int launch_mul_ragged(int rows, int k, const uint8_t *coeffs, const ListStripe *d_stripes, const uint32_t *d_tile_stripe,
                       const uint32_t *d_stripe_tile0, int64_t ntiles, int num_cus, void *stream);
-// Mixed-pattern recover (nxec_rs_recover_stripes_mixed): every stripe of the
-// batch names its own erased chunks.  Host half (nxec_recover_mixed_host.cpp,
-// pure arithmetic, no device): the distinct patterns, one nxec_rs_plan each.
+// Mixed-pattern recover and decode (nxec_rs_recover_stripes_mixed,
+// nxec_rs_decode_stripes_mixed): every stripe of the batch names its own erased
+// chunks.  Recover rebuilds every erased chunk in place; Decode, its
+// full-output form, sends all k data chunks of every decodable stripe to a
+// separate output.  Host half (nxec_mixed_host.cpp, pure arithmetic, no
+// device): the distinct plans, one matrix each.
+//   Recover: a plan is keyed by its erased set and holds nxec_rs_plan's repair
+//   rows for every erased id; a stripe with nothing erased has no plan.
+//   Decode: a plan is keyed by its input set, the first k alive ids: the erased
+//   data chunks are exactly the data ids missing from it, so stripes that
+//   differ only in erased chunks beyond their k-th alive one share a plan; a
+//   stripe with no lost data chunk still has one (k copies, no rows).
+enum class MixedMode { Recover, Decode };
 struct MixedPlan {
-  struct Pattern {
-    std::vector<int32_t> erased;  // ascending ids, 1 .. n-k of them
-    std::vector<int32_t> inputs;  // the first k alive ids
-    std::vector<uint8_t> rows;    // |erased| x k repair matrix (nxec_rs_plan)
-  };
-  std::vector<Pattern> patterns;    // decodable patterns, in order of first appearance
-  std::vector<int32_t> pattern_of;  // per stripe: index into patterns, -1 when nothing is coded
-  int64_t nsegments = 0;            // sum over the patterns of ceil(|erased| / kMaxRowsPerPass)
-  int64_t ncoded = 0;               // stripes with result > 0
-};
-// result[s] (nstripes entries, may be NULL) as nxec_rs_recover_stripes_mixed
-// documents it; arguments are validated by the caller.
-void mixed_plan(int n, int k, const uint8_t *alive, int64_t nstripes, int32_t *result, MixedPlan *plan);
-// One segment of a pattern as the kernel reads it: <= 4 repair rows over the
-// pattern's k sources, 32-bit byte offsets inside a stripe like MulArgs.
-// Coefficient rows >= rows are zero.
-struct MixedSeg {
-  uint32_t rows;
-  uint32_t dst_off[kMaxRowsPerPass];
-  uint32_t src_off[kMaxRaggedK];
-  uint8_t coef[kMaxRowsPerPass * kMaxRaggedK];  // row-major rows x k
-  uint8_t pad[4];
-};
-static_assert(sizeof(MixedSeg) % 16 == 0, "segment records are staged 16-byte aligned");
-// The device tables of a plan (k <= kMaxRaggedK, chunk offsets below 4 GiB):
-// the segment records; order[i], the stripe of the i-th coded item (items run
-// by segment, then ascending stripe; a stripe with more than 4 erased chunks
-// appears once per segment of its pattern); seg_of[i], its segment.
-void mixed_tables(const MixedPlan &plan, int k, int64_t chunk_stride, std::vector<MixedSeg> &segs,
-                  std::vector<uint32_t> &order, std::vector<uint32_t> &seg_of);
-// The mixed kernel of k <= kMaxRaggedK and the dynamic LDS its launch asks for.
-const void *mixed_kernel(int k, int *lds_bytes);
-// One launch over nitems coded items of len bytes per chunk (a multiple of 16;
-// base, strides and offsets 16-byte aligned); tables in device memory.
-// nsegs / ncoded only go to the launch record.
-int launch_mul_mixed(int k, uint8_t *base, int64_t stripe_stride, int64_t len, const MixedSeg *d_segs,
-                     const uint32_t *d_order, const uint32_t *d_seg_of, int64_t nitems, int64_t nsegs, int64_t ncoded,
-                     int num_cus, void *stream);
-// Mixed-pattern decode (nxec_rs_decode_stripes_mixed): the full-output form of
-// the mixed recover.  Every stripe of the batch names its own erased chunks and
-// all k data chunks of every decodable stripe go to a separate output.  Host
-// half (nxec_decode_mixed_host.cpp, pure arithmetic, no device).  A decode plan
-// is keyed by its input set, the first k alive ids: the erased data chunks are
-// exactly the data ids missing from it, so stripes that differ only in erased
-// chunks beyond their k-th alive one share a plan.
-struct DecodePlan {
   struct Plan {
     std::vector<int32_t> inputs;   // the first k alive ids, ascending
-    std::vector<int32_t> targets;  // T: the erased data ids (ids < k not among the inputs), ascending
-    std::vector<int32_t> erased;   // every id below inputs[k-1] that is no input: the shortest `failed`
-                                   // list with which nxec_rs_decode_stripes makes this plan (by-runs path)
-    std::vector<uint8_t> rows;     // |T| x k rows of nxec_rs_decode_matrix
+    std::vector<int32_t> targets;  // T, ascending.  Recover: every erased id; Decode: the erased data ids
+    std::vector<int32_t> erased;   // the `failed` list with which the single-pattern call makes this plan (by-runs
+                                   // path).  Recover: every erased id; Decode: every id below inputs[k-1] that is no
+                                   // input, the shortest such list
+    std::vector<uint8_t> rows;     // |T| x k: nxec_rs_plan's repair rows / nxec_rs_decode_matrix's inverse rows
   };
   std::vector<Plan> plans;       // in order of first appearance
-  std::vector<int32_t> plan_of;  // per stripe: index into plans, -1 for a LOST or SINGULAR stripe
+  std::vector<int32_t> plan_of;  // per stripe: index into plans, -1 where nothing is launched (LOST, SINGULAR,
+                                 // Recover: nothing erased)
   int64_t nsegments = 0;         // sum over the plans of max(1, ceil(|T| / kMaxRowsPerPass))
-  int64_t ndecoded = 0;          // stripes with result >= 0
+  int64_t nstripes_planned = 0;  // stripes with a plan.  Recover: result > 0; Decode: result >= 0
 };
-// result[s] (nstripes entries, may be NULL) as nxec_rs_decode_stripes_mixed
-// documents it; arguments are validated by the caller.
-void decode_mixed_plan(int n, int k, const uint8_t *alive, int64_t nstripes, int32_t *result, DecodePlan *plan);
-// One segment of a decode plan as the kernel reads it: MixedSeg plus the
-// pass-through of surviving data chunks.  copy_off[j] is the output offset of
-// source j where that source is a data chunk, else kNoCopy; only the first
-// segment of a plan copies.  src_off are offsets inside a source stripe,
-// dst_off and copy_off inside an output stripe.  rows may be 0 (a plan with no
-// lost data chunk: k copies, no table lookup); coefficient rows >= rows are zero.
-struct DecodeSeg {
+// result[s] (nstripes entries, may be NULL) as nxec_rs_recover_stripes_mixed /
+// nxec_rs_decode_stripes_mixed document it; arguments are validated by the caller.
+void mixed_plan(MixedMode mode, int n, int k, const uint8_t *alive, int64_t nstripes, int32_t *result, MixedPlan *plan);
+// One segment of a plan as the kernel reads it: <= 4 rows over the plan's k
+// sources, 32-bit byte offsets like MulArgs: src_off inside a source stripe,
+// dst_off and copy_off inside an output stripe.  copy_off[j] (Decode) is the
+// output offset of source j where that source is a data chunk, else kNoCopy:
+// the pass-through of surviving data chunks; only the first segment of a plan
+// copies.  Recover records hold kNoCopy throughout and the in-place kernel
+// never reads them.  rows may be 0 (a Decode plan with no lost data chunk: k
+// copies, no table lookup); coefficient rows >= rows are zero.
+struct MixedSeg {
   uint32_t rows;
   uint32_t dst_off[kMaxRowsPerPass];
   uint32_t src_off[kMaxRaggedK];
@@ -281,23 +249,25 @@ struct DecodeSeg {
   uint8_t coef[kMaxRowsPerPass * kMaxRaggedK];  // row-major rows x k
   uint8_t pad[8];
 };
-static_assert(sizeof(DecodeSeg) % 16 == 0, "segment records are staged 16-byte aligned");
-// The device tables of a decode plan (k <= kMaxDecodeMixedK, source and output
-// chunk offsets below 4 GiB), like mixed_tables: items run by segment, then
-// ascending stripe; a stripe with more than 4 lost data chunks appears once per
-// segment of its plan.
-void decode_mixed_tables(const DecodePlan &plan, int k, int64_t chunk_stride, int64_t out_chunk_stride,
-                         std::vector<DecodeSeg> &segs, std::vector<uint32_t> &order, std::vector<uint32_t> &seg_of);
-// The widest k with a k_decode_mixed instantiation; wider k take the by-runs path.
-constexpr int kMaxDecodeMixedK = kMaxRaggedK;
-// The decode kernel of k <= kMaxDecodeMixedK and the dynamic LDS its launch asks for.
-const void *decode_mixed_kernel(int k, int *lds_bytes);
+static_assert(sizeof(MixedSeg) % 16 == 0, "segment records are staged 16-byte aligned");
+// The device tables of a plan (k <= kMaxRaggedK, source and output chunk
+// offsets below 4 GiB): the segment records; order[i], the stripe of the i-th
+// item (items run by segment, then ascending stripe; a stripe with more than 4
+// targets appears once per segment of its plan); seg_of[i], its segment.
+// Recover passes out_chunk_stride = chunk_stride and copy = false.
+void mixed_tables(const MixedPlan &plan, int k, int64_t chunk_stride, int64_t out_chunk_stride, bool copy,
+                  std::vector<MixedSeg> &segs, std::vector<uint32_t> &order, std::vector<uint32_t> &seg_of);
+// The mixed kernel of k <= kMaxRaggedK (wider k take the by-runs path), in
+// place (k_mul_mixed) or full-output (k_decode_mixed), and the dynamic LDS its
+// launch asks for.
+const void *mixed_kernel(int k, bool full, int *lds_bytes);
 // One launch over nitems items of len bytes per chunk (a multiple of 16; both
-// bases, all four strides and every offset 16-byte aligned); tables in device
-// memory.  nsegs / ndecoded only go to the launch record.
-int launch_decode_mixed(int k, const uint8_t *src, int64_t stripe_stride, uint8_t *dst, int64_t out_stripe_stride,
-                        int64_t len, const DecodeSeg *d_segs, const uint32_t *d_order, const uint32_t *d_seg_of,
-                        int64_t nitems, int64_t nsegs, int64_t ndecoded, int num_cus, void *stream);
+// bases, both strides and every offset 16-byte aligned); tables in device
+// memory.  In place (full = false): src == dst and the strides are equal.
+// nsegs / nstripes only go to the launch record.
+int launch_mixed(int k, bool full, const uint8_t *src, int64_t stripe_stride, uint8_t *dst, int64_t out_stripe_stride,
+                 int64_t len, const MixedSeg *d_segs, const uint32_t *d_order, const uint32_t *d_seg_of, int64_t nitems,
+                 int64_t nsegs, int64_t nstripes, int num_cus, void *stream);
 // Delta update (nxec_rs_update_stripes): byte ranges of data chunks are
 // overwritten and the parity follows by c(r,j) (x) (new ^ old).  Host half
 // (nxec_update_host.cpp, pure arithmetic, no device): validation, the rounds,

@@ -556,18 +556,37 @@ __global__ __launch_bounds__(kBlock) void k_mul_ragged(const RaggedArgs a) {
   tile_loop<K, PF, true, true>(load, run, a.ntiles, a.queue_slot, a.tiles_per_grab, tab + kLds / 4);
 }
 
-// --- mixed-pattern recover (nxec_rs_recover_stripes_mixed) ---
-// Every coded stripe names its own erased chunks.  Item i = stripe order[i]
-// under segment seg_of[i] (one pattern's <= 4 repair rows over its k sources);
-// tile t = column tile t % tps of item t / tps.  Items run by segment, so a
-// workgroup's tables stay valid for long stretches; where the segment of the
-// tile it is about to run differs from the resident one it rebuilds them from
-// the segment record.  The tile index is workgroup-uniform (tile_loop), so the
-// rebuild and its two barriers are too.  Item, stripe and segment stay in
-// SGPRs (scalar loads of uniform addresses); only the vector index is per lane.
+// --- mixed-pattern recover and decode (nxec_rs_recover_stripes_mixed, nxec_rs_decode_stripes_mixed) ---
+// Every stripe names its own erased chunks.  Item i = stripe order[i] under
+// segment seg_of[i] (one plan's <= 4 rows over its k sources); tile t = column
+// tile t % tps of item t / tps.  Items run by segment, so a workgroup's tables
+// stay valid for long stretches; where the segment of the tile it is about to
+// run differs from the resident one it rebuilds them from the segment record.
+// The tile index is workgroup-uniform (tile_loop), so the rebuild and its two
+// barriers are too.  Item, stripe and segment stay in SGPRs (scalar loads of
+// uniform addresses); only the vector index is per lane, and every address is
+// a uniform 64-bit base plus one 32-bit lane offset.
+//
+// FULL = false (k_mul_mixed, the recover) works in place: sources and rebuilt
+// chunks share one base and one stride (dst, dst_stripe_stride; the launch sets
+// src and its stride equal to them and the kernel does not read them).
+//
+// FULL = true (k_decode_mixed, the decode) adds a full output: the sources come
+// from a const batch (src, src_stripe_stride), all k data chunks of every
+// item's stripe go to a separate output (dst, dst_stripe_stride).  A segment
+// carries <= 4 inverse rows for the lost data chunks and, in the first segment
+// of a plan, the output offsets of the sources that are surviving data chunks,
+// which are stored from the registers that loaded them.  rows == 0 segments (no
+// lost data chunk: the bulk of a healthy read) are pure copies: they skip the
+// lookups and the row stores under a workgroup-uniform branch, build nothing
+// and leave `resident` unchanged, so the tables of the last rows > 0 segment
+// stay valid for its next tile, and a rows > 0 segment other than that one
+// always rebuilds.  The output never intersects the source (refused by the
+// host): tile_loop issues tile t+1's loads before tile t's stores.
 struct MixedArgs {
-  uint8_t *base;
-  int64_t stripe_stride;
+  const uint8_t *src;
+  uint8_t *dst;
+  int64_t src_stripe_stride, dst_stripe_stride;
   const MixedSeg *__restrict__ segs;
   const uint32_t *__restrict__ order;
   const uint32_t *__restrict__ seg_of;
@@ -587,14 +606,15 @@ __device__ __forceinline__ const __attribute__((address_space(4))) T *const_tabl
   return (const __attribute__((address_space(4))) T *)(reinterpret_cast<uintptr_t>(p));
 }
 
-template <int K, int R>
-__global__ __launch_bounds__(kBlock) void k_mul_mixed(const MixedArgs a) {
+template <int K, int R, bool FULL>
+__device__ __forceinline__ void mixed_body(const MixedArgs &a) {
   constexpr bool PF = ragged_prefetch(K);
   constexpr int kLds = table_bytes(K, R);
-  static_assert(R == default_r(K) && kLds + kRingBytes == mixed_lds(K), "mixed kernels are queue-driven");
+  static_assert(K <= kMaxRaggedK && R == default_r(K) && kLds + kRingBytes == mixed_lds(K),
+                "mixed kernels are queue-driven");
   extern __shared__ uint32_t tab[];
   const char *tl = reinterpret_cast<const char *>(tab) + (threadIdx.x % R) * 4;
-  uint32_t resident = ~0u;  // the segment whose tables are in LDS (none yet)
+  uint32_t resident = ~0u;  // the (FULL: rows > 0) segment whose tables are in LDS (none yet)
   struct Where {
     uint32_t s, g, v;
   };
@@ -612,98 +632,10 @@ __global__ __launch_bounds__(kBlock) void k_mul_mixed(const MixedArgs a) {
     const Where w = where(t);
     if (w.v < a.nvec) {
       const auto *sg = const_table(a.segs) + w.g;
-      const uint8_t *sb = a.base + static_cast<int64_t>(w.s) * a.stripe_stride;
+      const uint8_t *sb;
+      if constexpr (FULL) sb = a.src + static_cast<int64_t>(w.s) * a.src_stripe_stride;
+      else sb = a.dst + static_cast<int64_t>(w.s) * a.dst_stripe_stride;
       // uniform 64-bit base + one 32-bit lane offset (chunks of a stripe lie within 4 GiB)
-      const uint32_t vo = w.v * 16u;
-#pragma unroll
-      for (int j = 0; j < K; j++) d[j] = ld_stream(sb + sg->src_off[j] + vo);
-    }
-  };
-  auto run = [&](uint32_t t, const u32x4(&d)[K]) {
-    const Where w = where(t);
-    const auto *sg = const_table(a.segs) + w.g;
-    const int rows = static_cast<int>(sg->rows);
-    if (w.g != resident) {  // workgroup-uniform
-      // no wave may still be looking up the previous tile; LDS-only fences, so
-      // the loads and stores in flight are not drained (tile_loop's ring_barrier)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-      __builtin_amdgcn_s_barrier();
-      build_tables<R>(a.segs[w.g].coef, K, rows, tab);  // rows >= the record's: zero products
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-      resident = w.g;
-    }
-    if (w.v < a.nvec) {
-      uint32_t acc[16];
-      lookup_sources<K, R>(tl, d, acc);
-      uint8_t *db = a.base + static_cast<int64_t>(w.s) * a.stripe_stride;
-      const uint32_t vo = w.v * 16u;
-      const uint32_t o0 = sg->dst_off[0], o1 = sg->dst_off[1], o2 = sg->dst_off[2], o3 = sg->dst_off[3];
-      store_rows(acc, rows, [=](int r) { return db + (r == 0 ? o0 : r == 1 ? o1 : r == 2 ? o2 : o3) + vo; });
-    }
-  };
-  // wave 0 (lane 0 = the tile's first vector) always issues its K loads: every tile has at least one vector
-  tile_loop<K, PF, true, true>(load, run, a.ntiles, a.queue_slot, a.tiles_per_grab, tab + kLds / 4);
-}
-
-// --- mixed-pattern decode (nxec_rs_decode_stripes_mixed) ---
-// k_mul_mixed's item / segment scheme with a full output: the sources come from
-// a const batch (src, stripe_stride), all k data chunks of every item's stripe
-// go to a separate output (dst, out_stripe_stride).  A segment carries <= 4
-// inverse rows for the lost data chunks and, in the first segment of a plan,
-// the output offsets of the sources that are surviving data chunks, which are
-// stored from the registers that loaded them.  Both bases stay uniform 64-bit
-// values (SGPRs) with one 32-bit lane offset, as in k_mul_mixed.
-//
-// rows == 0 segments (no lost data chunk: the bulk of a healthy read) are pure
-// copies: they skip the lookups and the row stores under a workgroup-uniform
-// branch, build nothing and leave `resident` unchanged, so the tables of the
-// last rows > 0 segment stay valid for its next tile, and a rows > 0 segment
-// other than that one always rebuilds.
-//
-// The output never intersects the source (refused by the host): tile_loop
-// issues tile t+1's loads before tile t's stores.
-struct DecodeMixedArgs {
-  const uint8_t *__restrict__ src;
-  uint8_t *__restrict__ dst;
-  int64_t src_stripe_stride, dst_stripe_stride;
-  const DecodeSeg *__restrict__ segs;
-  const uint32_t *__restrict__ order;
-  const uint32_t *__restrict__ seg_of;
-  uint32_t ntiles, tps, nvec;
-  int32_t queue_slot;
-  uint32_t tiles_per_grab;
-};
-
-constexpr int decode_mixed_lds(int k) { return vec_lds(k, default_r(k)); }
-
-template <int K, int R>
-__global__ __launch_bounds__(kBlock) void k_decode_mixed(const DecodeMixedArgs a) {
-  constexpr bool PF = ragged_prefetch(K);
-  constexpr int kLds = table_bytes(K, R);
-  static_assert(K <= kMaxDecodeMixedK && R == default_r(K) && kLds + kRingBytes == decode_mixed_lds(K),
-                "decode kernels are queue-driven");
-  extern __shared__ uint32_t tab[];
-  const char *tl = reinterpret_cast<const char *>(tab) + (threadIdx.x % R) * 4;
-  uint32_t resident = ~0u;  // the rows > 0 segment whose tables are in LDS (none yet)
-  struct Where {
-    uint32_t s, g, v;
-  };
-  auto where = [&](uint32_t t) -> Where {
-    const uint32_t i = t / a.tps;
-    // readfirstlane: stripe and segment (and every address made from them) belong in SGPRs (k_mul_mixed)
-    return {static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(const_table(a.order)[i])),
-            static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(const_table(a.seg_of)[i])),
-            (t - i * a.tps) * kBlock + threadIdx.x};
-  };
-  // a prefetched tile may belong to another segment than the resident one:
-  // its source offsets come from its own record
-  auto load = [&](uint32_t t, u32x4(&d)[K]) {
-    const Where w = where(t);
-    if (w.v < a.nvec) {
-      const auto *sg = const_table(a.segs) + w.g;
-      const uint8_t *sb = a.src + static_cast<int64_t>(w.s) * a.src_stripe_stride;
       const uint32_t vo = w.v * 16u;
 #pragma unroll
       for (int j = 0; j < K; j++) d[j] = ld_stream(sb + sg->src_off[j] + vo);
@@ -714,7 +646,8 @@ __global__ __launch_bounds__(kBlock) void k_decode_mixed(const DecodeMixedArgs a
     // the tile's own record: row count, row offsets and copy offsets (never the resident segment's)
     const auto *sg = const_table(a.segs) + w.g;
     const int rows = static_cast<int>(sg->rows);
-    if (rows > 0 && w.g != resident) {  // workgroup-uniform
+    const bool coded = !FULL || rows > 0;  // workgroup-uniform
+    if (coded && w.g != resident) {        // workgroup-uniform
       // no wave may still be looking up the previous tile; LDS-only fences, so
       // the loads and stores in flight are not drained (tile_loop's ring_barrier)
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
@@ -728,22 +661,42 @@ __global__ __launch_bounds__(kBlock) void k_decode_mixed(const DecodeMixedArgs a
     if (w.v < a.nvec) {
       uint8_t *db = a.dst + static_cast<int64_t>(w.s) * a.dst_stripe_stride;
       const uint32_t vo = w.v * 16u;
-      if (rows > 0) {  // workgroup-uniform
+      if (coded) {
         uint32_t acc[16];
         lookup_sources<K, R>(tl, d, acc);
         const uint32_t o0 = sg->dst_off[0], o1 = sg->dst_off[1], o2 = sg->dst_off[2], o3 = sg->dst_off[3];
         store_rows(acc, rows, [=](int r) { return db + (r == 0 ? o0 : r == 1 ? o1 : r == 2 ? o2 : o3) + vo; });
       }
+      if constexpr (FULL) {
 #pragma unroll
-      for (int j = 0; j < K; j++) {
-        const uint32_t c = sg->copy_off[j];  // scalar; kNoCopy in every later segment of a plan
-        if (c != kNoCopy) st_stream(db + c + vo, d[j]);
+        for (int j = 0; j < K; j++) {
+          const uint32_t c = sg->copy_off[j];  // scalar; kNoCopy in every later segment of a plan
+          if (c != kNoCopy) st_stream(db + c + vo, d[j]);
+        }
       }
     }
   };
   // QWAIT_K: every tile has at least one vector, so wave 0 (lane 0 = the tile's first vector) always issues its
   // K loads after the grab; the row stores and the copies only add vector-memory operations after them
   tile_loop<K, PF, true, true>(load, run, a.ntiles, a.queue_slot, a.tiles_per_grab, tab + kLds / 4);
+}
+
+// The two entry points of the one body.  They keep the names of the two
+// kernels they replace, and the decode's keeps an argument type of its own:
+// the length of the kernels' symbol names decides where `.text` begins in the
+// code object, and with every kernel of this file 0x300 bytes lower (one entry
+// point `k_mixed<K, R, FULL>`, shorter names) every leg of
+// tools/decode_mixed_rate.py, the untouched k_mul_vec copy form among them, ran
+// 1.3-2.9 % slower ("One planner, one record, one kernel").
+struct DecodeMixedArgs : MixedArgs {};
+
+template <int K, int R>
+__global__ __launch_bounds__(kBlock) void k_mul_mixed(const MixedArgs a) {
+  mixed_body<K, R, false>(a);
+}
+template <int K, int R>
+__global__ __launch_bounds__(kBlock) void k_decode_mixed(const DecodeMixedArgs a) {
+  mixed_body<K, R, true>(a);
 }
 
 // --- delta update (nxec_rs_update_stripes) ---
@@ -1258,20 +1211,21 @@ constexpr std::array<RaggedFn, sizeof...(Ks)> ragged_table(std::integer_sequence
 }
 const std::array<RaggedFn, kMaxRaggedK> kRagged = ragged_table(std::make_integer_sequence<int, kMaxRaggedK>{});
 
-using MixedFn = void (*)(MixedArgs);
 template <int... Ks>
-constexpr std::array<MixedFn, sizeof...(Ks)> mixed_table(std::integer_sequence<int, Ks...>) {
-  return {{&k_mul_mixed<Ks + 1, default_r(Ks + 1)>...}};
+constexpr auto mixed_table(std::integer_sequence<int, Ks...>) {
+  return std::array<void (*)(MixedArgs), sizeof...(Ks)>{{&k_mul_mixed<Ks + 1, default_r(Ks + 1)>...}};
 }
-const std::array<MixedFn, kMaxRaggedK> kMixed = mixed_table(std::make_integer_sequence<int, kMaxRaggedK>{});
-
-using DecodeMixedFn = void (*)(DecodeMixedArgs);
 template <int... Ks>
-constexpr std::array<DecodeMixedFn, sizeof...(Ks)> decode_mixed_table(std::integer_sequence<int, Ks...>) {
-  return {{&k_decode_mixed<Ks + 1, default_r(Ks + 1)>...}};
+constexpr auto decode_mixed_table(std::integer_sequence<int, Ks...>) {
+  return std::array<void (*)(DecodeMixedArgs), sizeof...(Ks)>{{&k_decode_mixed<Ks + 1, default_r(Ks + 1)>...}};
 }
-const std::array<DecodeMixedFn, kMaxDecodeMixedK> kDecodeMixed =
-    decode_mixed_table(std::make_integer_sequence<int, kMaxDecodeMixedK>{});
+const auto kMixed = mixed_table(std::make_integer_sequence<int, kMaxRaggedK>{});
+const auto kDecodeMixed = decode_mixed_table(std::make_integer_sequence<int, kMaxRaggedK>{});
+const void *mixed_fn(int k, bool full) {
+  return full ? reinterpret_cast<const void *>(kDecodeMixed[k - 1]) : reinterpret_cast<const void *>(kMixed[k - 1]);
+}
+// [full]: the launch-record families
+constexpr const char *kMixedFamily[2] = {"k_mul_mixed", "k_decode_mixed"};
 
 // two update kernels, each prepared at the largest k it serves: R = 16 while default_r(k) is 16, R = 8 up to kMaxRaggedK
 using UpdateFn = void (*)(UpdateArgs);
@@ -1332,10 +1286,9 @@ void list_kernels(std::vector<KernelLds> &out) {
   out.push_back({reinterpret_cast<const void *>(&k_scrub_bytes), "k_scrub_bytes", bytes_lds(NXEC_MAX_K), false});
   list_table(out, kRagged, "k_mul_ragged", ragged_lds);
   // the mixed kernels' tables start at dynamic LDS byte 0: no static LDS
-  for (int k = 1; k <= kMaxRaggedK; k++)
-    out.push_back({reinterpret_cast<const void *>(kMixed[k - 1]), "k_mul_mixed", mixed_lds(k), true});
-  for (int k = 1; k <= kMaxDecodeMixedK; k++)
-    out.push_back({reinterpret_cast<const void *>(kDecodeMixed[k - 1]), "k_decode_mixed", decode_mixed_lds(k), true});
+  for (int full = 0; full < 2; full++)
+    for (int k = 1; k <= kMaxRaggedK; k++)
+      out.push_back({mixed_fn(k, full), kMixedFamily[full], mixed_lds(k), true});
   // like them, the update kernels index their tables from dynamic LDS byte 0
   out.push_back({reinterpret_cast<const void *>(update_fn(kUpdateMaxK16)), "k_update_vec", update_lds(kUpdateMaxK16), true});
   out.push_back({reinterpret_cast<const void *>(update_fn(kMaxRaggedK)), "k_update_vec", update_lds(kMaxRaggedK), true});
@@ -1394,14 +1347,9 @@ const void *ragged_kernel(int k, int *lds_bytes) {
   return reinterpret_cast<const void *>(kRagged[k - 1]);
 }
 
-const void *mixed_kernel(int k, int *lds_bytes) {
+const void *mixed_kernel(int k, bool full, int *lds_bytes) {
   *lds_bytes = mixed_lds(k);
-  return reinterpret_cast<const void *>(kMixed[k - 1]);
-}
-
-const void *decode_mixed_kernel(int k, int *lds_bytes) {
-  *lds_bytes = decode_mixed_lds(k);
-  return reinterpret_cast<const void *>(kDecodeMixed[k - 1]);
+  return mixed_fn(k, full);
 }
 
 const void *update_vec_kernel(int k, int *lds_bytes) {
@@ -1720,40 +1668,15 @@ int launch_mul_ragged(int rows, int k, const uint8_t *coeffs, const ListStripe *
   return NXEC_OK;
 }
 
-int launch_mul_mixed(int k, uint8_t *base, int64_t stripe_stride, int64_t len, const MixedSeg *d_segs,
-                     const uint32_t *d_order, const uint32_t *d_seg_of, int64_t nitems, int64_t nsegs, int64_t ncoded,
-                     int num_cus, void *stream) {
+int launch_mixed(int k, bool full, const uint8_t *src, int64_t stripe_stride, uint8_t *dst, int64_t out_stripe_stride,
+                 int64_t len, const MixedSeg *d_segs, const uint32_t *d_order, const uint32_t *d_seg_of, int64_t nitems,
+                 int64_t nsegs, int64_t nstripes, int num_cus, void *stream) {
   if (nitems <= 0 || len <= 0) return NXEC_OK;
-  if (k < 1 || k > kMaxRaggedK) return set_error(NXEC_ERR_INVALID, "mixed launch: k=%d unsupported", k);
+  const char *what = full ? "mixed decode launch" : "mixed launch";
+  if (k < 1 || k > kMaxRaggedK) return set_error(NXEC_ERR_INVALID, "%s: k=%d unsupported", what, k);
   const int64_t nvec = len / 16, tps = (nvec + kBlock - 1) / kBlock;
   if (len % 16 || nvec >= (int64_t(1) << 32) || tps * nitems >= (int64_t(1) << 32))
-    return set_error(NXEC_ERR_INVALID, "mixed launch: too many tiles or a sub-16-byte tail");
-  MixedArgs a{};
-  a.base = base;
-  a.stripe_stride = stripe_stride;
-  a.segs = d_segs;
-  a.order = d_order;
-  a.seg_of = d_seg_of;
-  a.tps = static_cast<uint32_t>(tps);
-  a.nvec = static_cast<uint32_t>(nvec);
-  a.ntiles = static_cast<uint32_t>(tps * nitems);
-  a.tiles_per_grab = tiles_per_grab(k, kMaxRowsPerPass, 0);
-  char tail[64];
-  std::snprintf(tail, sizeof tail, "segs=%lld stripes=%lld", static_cast<long long>(nsegs),
-                static_cast<long long>(ncoded));
-  QueueLaunch l{"k_mul_mixed", "k", k, kMaxRowsPerPass, default_r(k), -1, -1, -1, ragged_prefetch(k), 1,
-                a.tiles_per_grab, 0, std::min<int64_t>(num_cus, a.ntiles), mixed_lds(k), 0, tail};
-  return queue_launch(kMixed[k - 1], a, a.queue_slot, l, static_cast<hipStream_t>(stream));
-}
-
-int launch_decode_mixed(int k, const uint8_t *src, int64_t stripe_stride, uint8_t *dst, int64_t out_stripe_stride,
-                        int64_t len, const DecodeSeg *d_segs, const uint32_t *d_order, const uint32_t *d_seg_of,
-                        int64_t nitems, int64_t nsegs, int64_t ndecoded, int num_cus, void *stream) {
-  if (nitems <= 0 || len <= 0) return NXEC_OK;
-  if (k < 1 || k > kMaxDecodeMixedK) return set_error(NXEC_ERR_INVALID, "mixed decode launch: k=%d unsupported", k);
-  const int64_t nvec = len / 16, tps = (nvec + kBlock - 1) / kBlock;
-  if (len % 16 || nvec >= (int64_t(1) << 32) || tps * nitems >= (int64_t(1) << 32))
-    return set_error(NXEC_ERR_INVALID, "mixed decode launch: too many tiles or a sub-16-byte tail");
+    return set_error(NXEC_ERR_INVALID, "%s: too many tiles or a sub-16-byte tail", what);
   DecodeMixedArgs a{};
   a.src = src;
   a.dst = dst;
@@ -1765,14 +1688,15 @@ int launch_decode_mixed(int k, const uint8_t *src, int64_t stripe_stride, uint8_
   a.tps = static_cast<uint32_t>(tps);
   a.nvec = static_cast<uint32_t>(nvec);
   a.ntiles = static_cast<uint32_t>(tps * nitems);
-  // a tile of a plan's first segment loads k pieces and stores k: its rows and its copies together
-  a.tiles_per_grab = tiles_per_grab(k, 0, k);
+  // full: a tile of a plan's first segment loads k pieces and stores k: its rows and its copies together
+  a.tiles_per_grab = full ? tiles_per_grab(k, 0, k) : tiles_per_grab(k, kMaxRowsPerPass, 0);
   char tail[64];
   std::snprintf(tail, sizeof tail, "segs=%lld stripes=%lld", static_cast<long long>(nsegs),
-                static_cast<long long>(ndecoded));
-  QueueLaunch l{"k_decode_mixed", "k", k, kMaxRowsPerPass, default_r(k), -1, -1, -1, ragged_prefetch(k), 1,
-                a.tiles_per_grab, 0, std::min<int64_t>(num_cus, a.ntiles), decode_mixed_lds(k), 0, tail};
-  return queue_launch(kDecodeMixed[k - 1], a, a.queue_slot, l, static_cast<hipStream_t>(stream));
+                static_cast<long long>(nstripes));
+  QueueLaunch l{kMixedFamily[full], "k", k, kMaxRowsPerPass, default_r(k), -1, -1, -1, ragged_prefetch(k), 1,
+                a.tiles_per_grab, 0, std::min<int64_t>(num_cus, a.ntiles), mixed_lds(k), 0, tail};
+  if (full) return queue_launch(kDecodeMixed[k - 1], a, a.queue_slot, l, static_cast<hipStream_t>(stream));
+  return queue_launch<MixedArgs>(kMixed[k - 1], a, a.queue_slot, l, static_cast<hipStream_t>(stream));
 }
 
 namespace {

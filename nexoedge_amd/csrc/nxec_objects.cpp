@@ -510,7 +510,7 @@ int nxec_decode_object_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned char 
     std::vector<int32_t> erased;
     for (int c = 0; c < n; c++)
       if (!a[c]) erased.push_back(c);
-    decode_mixed_plan(n, k, a, 1, &verdict[static_cast<size_t>(nf)], nullptr);
+    mixed_plan(MixedMode::Decode, n, k, a, 1, &verdict[static_cast<size_t>(nf)], nullptr);
     if (verdict[static_cast<size_t>(nf)] >= 0) {
       hipStream_t st = pick_stream(ctx, stream);
       rc = nxec_rs_decode_stripes(ctx, n, k, erased.data(), static_cast<int>(erased.size()), d_chunks + nf * stripe_stride,

@@ -142,41 +142,138 @@ static int scrub_coef(int device, int n, int k, const uint8_t *rows, const uint8
   return NXEC_OK;
 }
 
-// The device tables of a mixed launch (segment records, then order[], then
-// seg_of[], each 16-byte aligned) staged in a context slot that the stream
-// releases with an event: no host synchronisation on the caller's stream.
-// launch(d_segs, d_order, d_seg_of, count) enqueues `count` items; d_order and
-// d_seg_of already point at the first of them (a batch of more tiles than one
-// launch holds goes out in several).
-template <class Seg, class LaunchF>
-int staged_mixed_launch(nxec_ctx_t *ctx, const std::vector<Seg> &segs, const std::vector<uint32_t> &order,
-                               const std::vector<uint32_t> &seg_of, int64_t len, hipStream_t st, const LaunchF &launch) {
-  const size_t seg_bytes = segs.size() * sizeof(Seg);
-  const size_t item_bytes = (order.size() * sizeof(uint32_t) + 15) / 16 * 16;
+// Host tables of a launch sequence staged in a context slot that the stream
+// releases with an event: no host synchronisation on the caller's stream.  The
+// blocks go to the device in one copy, each at a 16-byte aligned offset;
+// body(d, off) enqueues the launches that read block i at d + off[i].
+struct HostBlock {
+  const void *p;
+  size_t bytes;
+};
+template <size_t N, class BodyF>
+int staged_launch(nxec_ctx_t *ctx, const HostBlock (&blocks)[N], hipStream_t st, const BodyF &body) {
+  size_t off[N], total = 0;
+  for (size_t i = 0; i < N; i++) {
+    off[i] = total;
+    total += (blocks[i].bytes + 15) / 16 * 16;
+  }
   Slot *slot = nullptr;
-  int rc = acquire_slot(ctx, seg_bytes + 2 * item_bytes, &slot, true);
+  int rc = acquire_slot(ctx, total, &slot, true);
   if (rc) return rc;
   // the slot's staging may still be in use by an earlier call on its own stream
   rc = hip_check(hipStreamSynchronize(slot->stream), "slot sync");
   if (!rc && !slot->busy) rc = hip_check(hipEventCreateWithFlags(&slot->busy, hipEventDisableTiming), "slot event");
   if (!rc) {
-    std::memcpy(slot->h, segs.data(), seg_bytes);
-    std::memcpy(slot->h + seg_bytes, order.data(), order.size() * sizeof(uint32_t));
-    std::memcpy(slot->h + seg_bytes + item_bytes, seg_of.data(), seg_of.size() * sizeof(uint32_t));
-    rc = hip_check(hipMemcpyAsync(slot->d, slot->h, seg_bytes + 2 * item_bytes, hipMemcpyHostToDevice, st), "tables H2D");
+    for (size_t i = 0; i < N; i++)
+      if (blocks[i].bytes) std::memcpy(slot->h + off[i], blocks[i].p, blocks[i].bytes);
+    rc = hip_check(hipMemcpyAsync(slot->d, slot->h, total, hipMemcpyHostToDevice, st), "tables H2D");
   }
   hipEvent_t kt[2];
   kt_begin(ctx, st, kt);
-  const int64_t per = max_stripes_per_launch(len / 16), nitems = static_cast<int64_t>(order.size());
-  for (int64_t i0 = 0; i0 < nitems && !rc; i0 += per)
-    rc = launch(reinterpret_cast<const Seg *>(slot->d), reinterpret_cast<const uint32_t *>(slot->d + seg_bytes) + i0,
-                reinterpret_cast<const uint32_t *>(slot->d + seg_bytes + item_bytes) + i0, std::min(per, nitems - i0));
+  if (!rc) rc = body(static_cast<const uint8_t *>(slot->d), off);
   kt_end(ctx, kt, st);
   // the tables stay in the slot until the stream gets past the launches
   if (!rc) rc = hip_check(hipEventRecord(slot->busy, st), "slot event record");
   slot->busy_set = !rc;
   if (rc) (void)hipStreamSynchronize(st);
   release_slot(ctx, slot);
+  return rc;
+}
+
+// The device tables of a mixed launch: segment records, then order[], then
+// seg_of[].  launch(d_segs, d_order, d_seg_of, count) enqueues `count` items;
+// d_order and d_seg_of already point at the first of them (a batch of more
+// tiles than one launch holds goes out in several).
+template <class LaunchF>
+int staged_mixed_launch(nxec_ctx_t *ctx, const std::vector<MixedSeg> &segs, const std::vector<uint32_t> &order,
+                        const std::vector<uint32_t> &seg_of, int64_t len, hipStream_t st, const LaunchF &launch) {
+  const HostBlock blocks[3] = {{segs.data(), segs.size() * sizeof(MixedSeg)},
+                               {order.data(), order.size() * sizeof(uint32_t)},
+                               {seg_of.data(), seg_of.size() * sizeof(uint32_t)}};
+  return staged_launch(ctx, blocks, st, [&](const uint8_t *d, const size_t(&off)[3]) {
+    const int64_t per = max_stripes_per_launch(len / 16), nitems = static_cast<int64_t>(order.size());
+    int rc = NXEC_OK;
+    for (int64_t i0 = 0; i0 < nitems && !rc; i0 += per)
+      rc = launch(reinterpret_cast<const MixedSeg *>(d + off[0]), reinterpret_cast<const uint32_t *>(d + off[1]) + i0,
+                  reinterpret_cast<const uint32_t *>(d + off[2]) + i0, std::min(per, nitems - i0));
+    return rc;
+  });
+}
+
+// By-runs path of the mixed recover and decode: run(erased, s0, count), the
+// single-pattern call, once per maximal run of consecutive stripes with an
+// equal plan (any k, alignment and length).  The plan's `erased` list makes
+// exactly its inputs; Decode's clean runs have a plan too.
+template <class RunF>
+int mixed_by_runs(const MixedPlan &plan, int64_t nstripes, const RunF &run) {
+  for (int64_t s0 = 0; s0 < nstripes;) {
+    const int32_t pi = plan.plan_of[s0];
+    int64_t s1 = s0 + 1;
+    while (s1 < nstripes && plan.plan_of[s1] == pi) s1++;
+    if (pi >= 0)
+      if (int rc = run(plan.plans[pi].erased, s0, s1 - s0)) return rc;
+    s0 = s1;
+  }
+  return NXEC_OK;
+}
+
+// One-launch path: the plan's tables staged in a slot, then k_mul_mixed (in place) or k_decode_mixed.
+static int mixed_one_launch(nxec_ctx_t *ctx, MixedMode mode, int k, const MixedPlan &plan, const unsigned char *src,
+                            int64_t cs, int64_t ss, unsigned char *dst, int64_t ocs, int64_t oss, int64_t len,
+                            hipStream_t st) {
+  const bool full = mode == MixedMode::Decode;
+  std::vector<MixedSeg> segs;
+  std::vector<uint32_t> order, seg_of;
+  mixed_tables(plan, k, cs, ocs, full, segs, order, seg_of);
+  return staged_mixed_launch(ctx, segs, order, seg_of, len, st,
+                             [&](const MixedSeg *d_segs, const uint32_t *d_order, const uint32_t *d_seg_of, int64_t count) {
+                               return launch_mixed(k, full, src, ss, dst, oss, len, d_segs, d_order, d_seg_of, count,
+                                                   static_cast<int64_t>(segs.size()), plan.nstripes_planned,
+                                                   ctx->num_cus, st);
+                             });
+}
+
+// The body of nxec_rs_recover_stripes_mixed (src == dst, equal strides) and
+// nxec_rs_decode_stripes_mixed after their argument checks: plan, one launch
+// or by runs, verdicts.
+static int mixed_stripes(nxec_ctx_t *ctx, MixedMode mode, int n, int k, const unsigned char *alive,
+                         const unsigned char *src, int64_t cs, int64_t ss, unsigned char *dst, int64_t ocs, int64_t oss,
+                         int64_t len, int64_t nstripes, int32_t *result, void *stream) {
+  // stripe ids are 32-bit in the device tables: larger batches go block by block
+  constexpr int64_t kBlockStripes = int64_t(1) << 31;
+  if (nstripes > kBlockStripes) {
+    for (int64_t s0 = 0; s0 < nstripes; s0 += kBlockStripes)
+      if (int rc = mixed_stripes(ctx, mode, n, k, alive + s0 * n, src ? src + s0 * ss : nullptr, cs, ss,
+                                 dst ? dst + s0 * oss : nullptr, ocs, oss, len, std::min(kBlockStripes, nstripes - s0),
+                                 result ? result + s0 : nullptr, stream))
+        return rc;
+    return NXEC_OK;
+  }
+  const bool recover = mode == MixedMode::Recover;
+  std::vector<int32_t> verdict(static_cast<size_t>(nstripes));
+  MixedPlan plan;
+  mixed_plan(mode, n, k, alive, nstripes, verdict.data(), &plan);
+  const bool work = plan.nstripes_planned > 0 && len > 0;
+  if (work && (!src || !dst)) return set_error(NXEC_ERR_INVALID, "null stripe buffer");
+  // chunk byte offsets inside a stripe stay 32-bit (the kernels' scalar address math); the decode checked before planning
+  if (recover && work && (cs < 0 || static_cast<int64_t>(n - 1) * cs + len > (int64_t(1) << 32) - 1))
+    return set_error(NXEC_ERR_INVALID, "mixed recover: chunk offset out of range (chunks of a stripe must lie within 4 GiB)");
+  int rc = NXEC_OK;
+  if (work) {
+    if ((rc = ensure_device(ctx->device))) return rc;
+    const bool one_launch = k <= kMaxRaggedK && aligned16(src) && aligned16(dst) && cs % 16 == 0 && ss % 16 == 0 &&
+                            ocs % 16 == 0 && oss % 16 == 0 && len % 16 == 0;
+    if (one_launch)
+      rc = mixed_one_launch(ctx, mode, k, plan, src, cs, ss, dst, ocs, oss, len, pick_stream(ctx, stream));
+    else
+      rc = mixed_by_runs(plan, nstripes, [&](const std::vector<int32_t> &e, int64_t s0, int64_t count) {
+        const int ne = static_cast<int>(e.size());
+        return recover ? nxec_rs_recover_stripes(ctx, n, k, e.data(), ne, dst + s0 * ss, cs, ss, len, count, stream)
+                       : nxec_rs_decode_stripes(ctx, n, k, e.data(), ne, src + s0 * ss, cs, ss, dst + s0 * oss, ocs, oss,
+                                                len, count, stream);
+      });
+  }
+  if (result && nstripes > 0) std::memcpy(result, verdict.data(), verdict.size() * sizeof(int32_t));
   return rc;
 }
 
@@ -244,38 +341,6 @@ int nxec_rs_recover_stripes(nxec_ctx_t *ctx, int n, int k, const int32_t *failed
                           d_stripes, failed, chunk_stride, stripe_stride, nullptr, len, nstripes, stream);
 }
 
-// By-runs path of the mixed recover: one nxec_rs_recover_stripes per maximal
-// run of consecutive stripes with equal pattern (any k, alignment and length).
-static int recover_mixed_by_runs(nxec_ctx_t *ctx, int n, int k, const MixedPlan &plan, unsigned char *d_stripes,
-                                 int64_t cs, int64_t ss, int64_t len, int64_t nstripes, void *stream) {
-  for (int64_t s0 = 0; s0 < nstripes;) {
-    const int32_t pi = plan.pattern_of[s0];
-    int64_t s1 = s0 + 1;
-    while (s1 < nstripes && plan.pattern_of[s1] == pi) s1++;
-    if (pi >= 0) {
-      const std::vector<int32_t> &e = plan.patterns[pi].erased;
-      if (int rc = nxec_rs_recover_stripes(ctx, n, k, e.data(), static_cast<int>(e.size()), d_stripes + s0 * ss, cs,
-                                           ss, len, s1 - s0, stream))
-        return rc;
-    }
-    s0 = s1;
-  }
-  return NXEC_OK;
-}
-
-// One-launch path of the mixed recover.
-static int recover_mixed_one_launch(nxec_ctx_t *ctx, int k, const MixedPlan &plan, unsigned char *d_stripes,
-                                    int64_t cs, int64_t ss, int64_t len, hipStream_t st) {
-  std::vector<MixedSeg> segs;
-  std::vector<uint32_t> order, seg_of;
-  mixed_tables(plan, k, cs, segs, order, seg_of);
-  return staged_mixed_launch(ctx, segs, order, seg_of, len, st,
-                             [&](const MixedSeg *d_segs, const uint32_t *d_order, const uint32_t *d_seg_of, int64_t count) {
-                               return launch_mul_mixed(k, d_stripes, ss, len, d_segs, d_order, d_seg_of, count,
-                                                       static_cast<int64_t>(segs.size()), plan.ncoded, ctx->num_cus, st);
-                             });
-}
-
 int nxec_rs_recover_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned char *alive,
                                   unsigned char *d_stripes, int64_t chunk_stride, int64_t stripe_stride, int64_t len,
                                   int64_t nstripes, int32_t *result, void *stream) {
@@ -283,40 +348,12 @@ int nxec_rs_recover_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned 
   if (!valid_nk(n, k)) return set_error(NXEC_ERR_INVALID, "invalid (n,k)=(%d,%d)", n, k);
   if (len < 0 || nstripes < 0) return set_error(NXEC_ERR_INVALID, "negative len or nstripes");
   if (!alive && nstripes > 0) return set_error(NXEC_ERR_INVALID, "mixed recover: null alive map");
-  // stripe ids are 32-bit in the device tables: larger batches go block by block
-  constexpr int64_t kBlockStripes = int64_t(1) << 31;
-  if (nstripes > kBlockStripes) {
-    for (int64_t s0 = 0; s0 < nstripes; s0 += kBlockStripes)
-      if (int rc = nxec_rs_recover_stripes_mixed(ctx, n, k, alive + s0 * n, d_stripes ? d_stripes + s0 * stripe_stride : nullptr,
-                                                 chunk_stride, stripe_stride, len, std::min(kBlockStripes, nstripes - s0),
-                                                 result ? result + s0 : nullptr, stream))
-        return rc;
-    return NXEC_OK;
-  }
-  std::vector<int32_t> verdict(static_cast<size_t>(nstripes));
-  MixedPlan plan;
-  mixed_plan(n, k, alive, nstripes, verdict.data(), &plan);
-  const bool work = plan.ncoded > 0 && len > 0;
-  if (work && !d_stripes) return set_error(NXEC_ERR_INVALID, "null stripe buffer");
-  // chunk byte offsets inside a stripe stay 32-bit (the kernels' scalar address math)
-  if (work && (chunk_stride < 0 || static_cast<int64_t>(n - 1) * chunk_stride + len > (int64_t(1) << 32) - 1))
-    return set_error(NXEC_ERR_INVALID, "mixed recover: chunk offset out of range (chunks of a stripe must lie within 4 GiB)");
-  int rc = NXEC_OK;
-  if (work) {
-    if ((rc = ensure_device(ctx->device))) return rc;
-    const bool one_launch = k <= kMaxRaggedK && aligned16(d_stripes) && chunk_stride % 16 == 0 &&
-                            stripe_stride % 16 == 0 && len % 16 == 0;
-    rc = one_launch ? recover_mixed_one_launch(ctx, k, plan, d_stripes, chunk_stride, stripe_stride, len,
-                                               pick_stream(ctx, stream))
-                    : recover_mixed_by_runs(ctx, n, k, plan, d_stripes, chunk_stride, stripe_stride, len, nstripes,
-                                            stream);
-  }
-  if (result && nstripes > 0) std::memcpy(result, verdict.data(), verdict.size() * sizeof(int32_t));
-  return rc;
+  return mixed_stripes(ctx, MixedMode::Recover, n, k, alive, d_stripes, chunk_stride, stripe_stride, d_stripes,
+                       chunk_stride, stripe_stride, len, nstripes, result, stream);
 }
 
 // Delta update: the planner's tables staged in a context slot that the stream
-// releases with an event (staged_mixed_launch's scheme), then per round
+// releases with an event (staged_launch), then per round
 // and per pass of <= 4 parity rows the vector launch and the byte launch.
 int nxec_rs_update_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripes, int64_t chunk_stride,
                            int64_t stripe_stride, int64_t len, int64_t nstripes, const nxec_update *updates,
@@ -334,48 +371,31 @@ int nxec_rs_update_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_strip
   nxec_gf_gen_rs_matrix(enc.data(), n, k);
   const uint8_t *parity = enc.data() + static_cast<size_t>(k) * k;  // (n-k) x k
 
-  const size_t item_bytes = plan.items.size() * sizeof(UpdateItem);
-  const size_t prefix_bytes = (plan.byte_prefix.size() * sizeof(int64_t) + 15) / 16 * 16;
-  const size_t tile_bytes = (plan.tile_item.size() * sizeof(uint32_t) + 15) / 16 * 16;
-  const size_t total = item_bytes + prefix_bytes + tile_bytes;
-  Slot *slot = nullptr;
-  if ((rc = acquire_slot(ctx, total, &slot, true))) return rc;
-  // the slot's staging may still be in use by an earlier call on its own stream
-  rc = hip_check(hipStreamSynchronize(slot->stream), "slot sync");
-  if (!rc && !slot->busy) rc = hip_check(hipEventCreateWithFlags(&slot->busy, hipEventDisableTiming), "slot event");
-  if (!rc) {
-    std::memcpy(slot->h, plan.items.data(), item_bytes);
-    std::memcpy(slot->h + item_bytes, plan.byte_prefix.data(), plan.byte_prefix.size() * sizeof(int64_t));
-    std::memcpy(slot->h + item_bytes + prefix_bytes, plan.tile_item.data(), plan.tile_item.size() * sizeof(uint32_t));
-    rc = hip_check(hipMemcpyAsync(slot->d, slot->h, total, hipMemcpyHostToDevice, st), "tables H2D");
-  }
-  const UpdateItem *d_items = reinterpret_cast<const UpdateItem *>(slot->d);
-  const int64_t *d_prefix = reinterpret_cast<const int64_t *>(slot->d + item_bytes);
-  const uint32_t *d_tiles = reinterpret_cast<const uint32_t *>(slot->d + item_bytes + prefix_bytes);
-  hipEvent_t kt[2];
-  kt_begin(ctx, st, kt);
-  const int m = n - k, passes = std::max(1, (m + kMaxRowsPerPass - 1) / kMaxRowsPerPass);
-  for (size_t r = 0; r < plan.rounds.size() && !rc; r++) {
-    const UpdateRound &rd = plan.rounds[r];
-    for (int p = 0; p < passes && !rc; p++) {
-      const int row0 = p * kMaxRowsPerPass, rows = std::min(kMaxRowsPerPass, m - row0);
-      const uint8_t *coef = parity + static_cast<size_t>(row0) * k;
-      const bool last = p == passes - 1;
-      rc = launch_update_vec(k, rows, row0, coef, d_stripes, chunk_stride, d_items, d_tiles + rd.tile0, rd.ntiles, last,
-                             rd.nupdates, static_cast<int>(r), p, ctx->num_cus, st);
-      if (!rc)
-        rc = launch_update_bytes(k, rows, row0, coef, d_stripes, chunk_stride, d_items + rd.byte_item0,
-                                 d_prefix + rd.prefix0, rd.nbyte_items, rd.nbytes, last, static_cast<int>(r), p,
-                                 ctx->num_cus, st);
+  const HostBlock blocks[3] = {{plan.items.data(), plan.items.size() * sizeof(UpdateItem)},
+                               {plan.byte_prefix.data(), plan.byte_prefix.size() * sizeof(int64_t)},
+                               {plan.tile_item.data(), plan.tile_item.size() * sizeof(uint32_t)}};
+  return staged_launch(ctx, blocks, st, [&](const uint8_t *d, const size_t(&off)[3]) {
+    const UpdateItem *d_items = reinterpret_cast<const UpdateItem *>(d + off[0]);
+    const int64_t *d_prefix = reinterpret_cast<const int64_t *>(d + off[1]);
+    const uint32_t *d_tiles = reinterpret_cast<const uint32_t *>(d + off[2]);
+    const int m = n - k, passes = std::max(1, (m + kMaxRowsPerPass - 1) / kMaxRowsPerPass);
+    int rc = NXEC_OK;
+    for (size_t r = 0; r < plan.rounds.size() && !rc; r++) {
+      const UpdateRound &rd = plan.rounds[r];
+      for (int p = 0; p < passes && !rc; p++) {
+        const int row0 = p * kMaxRowsPerPass, rows = std::min(kMaxRowsPerPass, m - row0);
+        const uint8_t *coef = parity + static_cast<size_t>(row0) * k;
+        const bool last = p == passes - 1;
+        rc = launch_update_vec(k, rows, row0, coef, d_stripes, chunk_stride, d_items, d_tiles + rd.tile0, rd.ntiles,
+                               last, rd.nupdates, static_cast<int>(r), p, ctx->num_cus, st);
+        if (!rc)
+          rc = launch_update_bytes(k, rows, row0, coef, d_stripes, chunk_stride, d_items + rd.byte_item0,
+                                   d_prefix + rd.prefix0, rd.nbyte_items, rd.nbytes, last, static_cast<int>(r), p,
+                                   ctx->num_cus, st);
+      }
     }
-  }
-  kt_end(ctx, kt, st);
-  // the tables stay in the slot until the stream gets past the launches
-  if (!rc) rc = hip_check(hipEventRecord(slot->busy, st), "slot event record");
-  slot->busy_set = !rc;
-  if (rc) (void)hipStreamSynchronize(st);
-  release_slot(ctx, slot);
-  return rc;
+    return rc;
+  });
 }
 
 int nxec_rs_scrub_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripes, int64_t chunk_stride,
@@ -481,41 +501,6 @@ int nxec_rs_decode_stripes(nxec_ctx_t *ctx, int n, int k, const int32_t *failed,
                           out_stripe_stride, copy.data(), len, nstripes, stream);
 }
 
-// By-runs path of the mixed decode: one nxec_rs_decode_stripes per maximal run
-// of consecutive stripes with an equal plan, clean runs included (any k,
-// alignment and length).  The plan's `erased` list makes exactly its inputs.
-static int decode_mixed_by_runs(nxec_ctx_t *ctx, int n, int k, const DecodePlan &plan, const unsigned char *d_stripes,
-                                int64_t cs, int64_t ss, unsigned char *d_out, int64_t ocs, int64_t oss, int64_t len,
-                                int64_t nstripes, void *stream) {
-  for (int64_t s0 = 0; s0 < nstripes;) {
-    const int32_t pi = plan.plan_of[s0];
-    int64_t s1 = s0 + 1;
-    while (s1 < nstripes && plan.plan_of[s1] == pi) s1++;
-    if (pi >= 0) {
-      const std::vector<int32_t> &e = plan.plans[pi].erased;
-      if (int rc = nxec_rs_decode_stripes(ctx, n, k, e.data(), static_cast<int>(e.size()), d_stripes + s0 * ss, cs, ss,
-                                          d_out + s0 * oss, ocs, oss, len, s1 - s0, stream))
-        return rc;
-    }
-    s0 = s1;
-  }
-  return NXEC_OK;
-}
-
-// One-launch path of the mixed decode: tables staged exactly as the mixed recover's.
-static int decode_mixed_one_launch(nxec_ctx_t *ctx, int k, const DecodePlan &plan, const unsigned char *d_stripes,
-                                   int64_t cs, int64_t ss, unsigned char *d_out, int64_t ocs, int64_t oss, int64_t len,
-                                   hipStream_t st) {
-  std::vector<DecodeSeg> segs;
-  std::vector<uint32_t> order, seg_of;
-  decode_mixed_tables(plan, k, cs, ocs, segs, order, seg_of);
-  return staged_mixed_launch(ctx, segs, order, seg_of, len, st,
-                             [&](const DecodeSeg *d_segs, const uint32_t *d_order, const uint32_t *d_seg_of, int64_t count) {
-                               return launch_decode_mixed(k, d_stripes, ss, d_out, oss, len, d_segs, d_order, d_seg_of, count,
-                                                          static_cast<int64_t>(segs.size()), plan.ndecoded, ctx->num_cus, st);
-                             });
-}
-
 int nxec_rs_decode_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned char *alive,
                                  const unsigned char *d_stripes, int64_t chunk_stride, int64_t stripe_stride,
                                  unsigned char *d_out, int64_t out_chunk_stride, int64_t out_stripe_stride,
@@ -541,36 +526,8 @@ int nxec_rs_decode_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned c
                           static_cast<__int128>(k - 1) * out_chunk_stride + len;
     if (dst0 < src1 && src0 < dst1) return set_error(NXEC_ERR_INVALID, "mixed decode: the output intersects the source");
   }
-  // stripe ids are 32-bit in the device tables: larger batches go block by block
-  constexpr int64_t kBlockStripes = int64_t(1) << 31;
-  if (nstripes > kBlockStripes) {
-    for (int64_t s0 = 0; s0 < nstripes; s0 += kBlockStripes)
-      if (int rc = nxec_rs_decode_stripes_mixed(ctx, n, k, alive + s0 * n, d_stripes ? d_stripes + s0 * stripe_stride : nullptr,
-                                                chunk_stride, stripe_stride, d_out ? d_out + s0 * out_stripe_stride : nullptr,
-                                                out_chunk_stride, out_stripe_stride, len,
-                                                std::min(kBlockStripes, nstripes - s0), result ? result + s0 : nullptr,
-                                                stream))
-        return rc;
-    return NXEC_OK;
-  }
-  std::vector<int32_t> verdict(static_cast<size_t>(nstripes));
-  DecodePlan plan;
-  decode_mixed_plan(n, k, alive, nstripes, verdict.data(), &plan);
-  const bool work = plan.ndecoded > 0 && len > 0;
-  if (work && (!d_stripes || !d_out)) return set_error(NXEC_ERR_INVALID, "null stripe buffer");
-  int rc = NXEC_OK;
-  if (work) {
-    if ((rc = ensure_device(ctx->device))) return rc;
-    const bool one_launch = k <= kMaxDecodeMixedK && aligned16(d_stripes) && aligned16(d_out) && chunk_stride % 16 == 0 &&
-                            stripe_stride % 16 == 0 && out_chunk_stride % 16 == 0 && out_stripe_stride % 16 == 0 &&
-                            len % 16 == 0;
-    rc = one_launch ? decode_mixed_one_launch(ctx, k, plan, d_stripes, chunk_stride, stripe_stride, d_out,
-                                              out_chunk_stride, out_stripe_stride, len, pick_stream(ctx, stream))
-                    : decode_mixed_by_runs(ctx, n, k, plan, d_stripes, chunk_stride, stripe_stride, d_out,
-                                           out_chunk_stride, out_stripe_stride, len, nstripes, stream);
-  }
-  if (result && nstripes > 0) std::memcpy(result, verdict.data(), verdict.size() * sizeof(int32_t));
-  return rc;
+  return mixed_stripes(ctx, MixedMode::Decode, n, k, alive, d_stripes, chunk_stride, stripe_stride, d_out,
+                       out_chunk_stride, out_stripe_stride, len, nstripes, result, stream);
 }
 
 int nxec_rs_car_repair_stripes(nxec_ctx_t *ctx, int n, int k, int failed, const int32_t *group_offsets,

@@ -1,6 +1,6 @@
 // Stand-alone host program for the planner of the mixed-pattern decode
-// (nxec_rs_decode_mixed_plan, nxec::decode_mixed_plan,
-// nxec::decode_mixed_tables): no device, no libnxec.  Built with
+// (nxec_rs_decode_mixed_plan, nxec::mixed_plan in Decode mode,
+// nxec::mixed_tables with copies): no device, no libnxec.  Built with
 // -fsanitize=address,undefined (make build/decode_mixed_plan_test) from the
 // planner source and gf_host.cpp.
 //
@@ -131,8 +131,8 @@ void enumerate(int n, int k, int64_t want_sets, int64_t want_singular) {
 // The device tables of `alive` against a brute-force walk of every item.
 void check_tables(int n, int k, const std::vector<unsigned char> &alive, int64_t ns, int64_t cs, int64_t ocs, int64_t len) {
   std::vector<int32_t> res(ns, 777);
-  nxec::DecodePlan plan;
-  nxec::decode_mixed_plan(n, k, alive.data(), ns, res.data(), &plan);
+  nxec::MixedPlan plan;
+  nxec::mixed_plan(nxec::MixedMode::Decode, n, k, alive.data(), ns, res.data(), &plan);
   std::set<std::vector<int32_t>> distinct;
   int64_t decoded = 0, segs = 0;
   for (int64_t s = 0; s < ns; s++) {
@@ -145,7 +145,7 @@ void check_tables(int n, int k, const std::vector<unsigned char> &alive, int64_t
     if (want < 0 || plan.plan_of[s] < 0) continue;
     decoded++;
     if (distinct.insert(in).second) segs += std::max(1, (want + 3) / 4);
-    const nxec::DecodePlan::Plan &pl = plan.plans[plan.plan_of[s]];
+    const nxec::MixedPlan::Plan &pl = plan.plans[plan.plan_of[s]];
     EXPECT(pl.inputs == in && pl.targets == t, "stripe %lld mapped to another plan", static_cast<long long>(s));
     // the by-runs list makes the same plan through nxec_rs_decode_stripes' own steps
     std::vector<int32_t> in2, t2;
@@ -153,12 +153,12 @@ void check_tables(int n, int k, const std::vector<unsigned char> &alive, int64_t
            static_cast<long long>(s));
     for (int32_t c : pl.erased) EXPECT(!alive[s * n + c], "stripe %lld: by-runs list erases a live chunk", static_cast<long long>(s));
   }
-  EXPECT(plan.ndecoded == decoded && plan.nsegments == segs && plan.plans.size() == distinct.size(),
+  EXPECT(plan.nstripes_planned == decoded && plan.nsegments == segs && plan.plans.size() == distinct.size(),
          "(%d,%d) counters", n, k);
-  if (k > nxec::kMaxDecodeMixedK) return;
-  std::vector<nxec::DecodeSeg> sg;
+  if (k > nxec::kMaxRaggedK) return;
+  std::vector<nxec::MixedSeg> sg;
   std::vector<uint32_t> order, seg_of;
-  nxec::decode_mixed_tables(plan, k, cs, ocs, sg, order, seg_of);
+  nxec::mixed_tables(plan, k, cs, ocs, true, sg, order, seg_of);
   EXPECT(static_cast<int64_t>(sg.size()) == segs && order.size() == seg_of.size(), "(%d,%d) table sizes", n, k);
   std::map<uint32_t, int> times;                    // stripe -> items
   std::map<uint32_t, std::vector<int>> produced;    // stripe -> times each data chunk is written
@@ -175,7 +175,7 @@ void check_tables(int n, int k, const std::vector<unsigned char> &alive, int64_t
     const bool first = first_seg.emplace(s, seg_of[i]).second;
     std::vector<int> &made = produced[s];
     made.resize(k, 0);
-    const nxec::DecodeSeg &g = sg[seg_of[i]];
+    const nxec::MixedSeg &g = sg[seg_of[i]];
     std::vector<int32_t> e, in, t;
     std::vector<unsigned char> rm;
     for (int c = 0; c < n; c++)

@@ -11,7 +11,9 @@
 //  * random maps of 10^4 stripes: verdicts and counters against a direct
 //    per-stripe evaluation, and the device tables' invariants (items by
 //    segment then ascending stripe, every coded stripe once per segment of its
-//    pattern, offsets and coefficient rows those of nxec_rs_plan, unused rows zero).
+//    pattern, offsets and coefficient rows those of nxec_rs_plan, unused rows zero);
+//  * one RS(6,4) batch of five stripes: every field of the device tables
+//    against values written out by hand, copy_off all kNoCopy.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -126,7 +128,7 @@ void random_maps(int n, int k, uint32_t seed, int max_erased) {
   }
   std::vector<int32_t> res(ns, 777);
   nxec::MixedPlan plan;
-  nxec::mixed_plan(n, k, alive.data(), ns, res.data(), &plan);
+  nxec::mixed_plan(nxec::MixedMode::Recover, n, k, alive.data(), ns, res.data(), &plan);
   std::set<std::vector<int32_t>> distinct;
   int64_t coded = 0, segs = 0;
   for (int64_t s = 0; s < ns; s++) {
@@ -135,19 +137,19 @@ void random_maps(int n, int k, uint32_t seed, int max_erased) {
       if (!alive[s * n + c]) e.push_back(c);
     const int want = direct(n, k, e, nullptr, nullptr);
     EXPECT(res[s] == want, "(%d,%d) random stripe %lld: %d, want %d", n, k, static_cast<long long>(s), res[s], want);
-    EXPECT((plan.pattern_of[s] >= 0) == (want > 0), "pattern_of of stripe %lld", static_cast<long long>(s));
+    EXPECT((plan.plan_of[s] >= 0) == (want > 0), "plan_of of stripe %lld", static_cast<long long>(s));
     if (want > 0) {
       coded++;
       if (distinct.insert(e).second) segs += (want + 3) / 4;
-      EXPECT(plan.patterns[plan.pattern_of[s]].erased == e, "stripe %lld mapped to another pattern", static_cast<long long>(s));
+      EXPECT(plan.plans[plan.plan_of[s]].erased == e, "stripe %lld mapped to another pattern", static_cast<long long>(s));
     }
   }
-  EXPECT(plan.ncoded == coded && plan.nsegments == segs && plan.patterns.size() == distinct.size(),
+  EXPECT(plan.nstripes_planned == coded && plan.nsegments == segs && plan.plans.size() == distinct.size(),
          "(%d,%d) random counters", n, k);
   if (k > nxec::kMaxRaggedK) return;
   std::vector<nxec::MixedSeg> sg;
   std::vector<uint32_t> order, seg_of;
-  nxec::mixed_tables(plan, k, cs, sg, order, seg_of);
+  nxec::mixed_tables(plan, k, cs, cs, false, sg, order, seg_of);
   EXPECT(static_cast<int64_t>(sg.size()) == segs && order.size() == seg_of.size(), "(%d,%d) table sizes", n, k);
   std::map<uint32_t, int> times;  // stripe -> items
   std::map<uint32_t, std::set<int32_t>> rebuilt;
@@ -160,7 +162,7 @@ void random_maps(int n, int k, uint32_t seed, int max_erased) {
     }
     times[order[i]]++;
     const nxec::MixedSeg &g = sg[seg_of[i]];
-    const nxec::MixedPlan::Pattern &pat = plan.patterns[plan.pattern_of[order[i]]];
+    const nxec::MixedPlan::Plan &pat = plan.plans[plan.plan_of[order[i]]];
     std::vector<int32_t> in;
     std::vector<unsigned char> rm;
     direct(n, k, pat.erased, &in, &rm);
@@ -189,9 +191,64 @@ void random_maps(int n, int k, uint32_t seed, int max_erased) {
   }
 }
 
+// The recover's device tables of one small batch against values written out by
+// hand: RS(6,4), chunk stride 64, erased sets {}, {0}, {0}, {1,5}, {0,1,2}.
+// Parity 4 is d0^d1^d2^d3 and parity 5 is d0 ^ 2 d1 ^ 4 d2 ^ 8 d3, so
+//   chunk 0 from 1,2,3,4:  d0 = d1 ^ d2 ^ d3 ^ p4                        rows {1,1,1,1}
+//   chunks 1,5 from 0,2,3,4: d1 = d0 ^ d2 ^ d3 ^ p4                      rows {1,1,1,1}
+//                            p5 = d0 ^ 2 (d0^d2^d3^p4) ^ 4 d2 ^ 8 d3          {3,6,10,2}
+// Recover records carry no copies: copy_off is kNoCopy throughout.
+void hand_tables() {
+  const int n = 6, k = 4;
+  const int64_t cs = 64;
+  unsigned char alive[5 * n];
+  std::memset(alive, 1, sizeof alive);
+  alive[1 * n + 0] = alive[2 * n + 0] = 0;
+  alive[3 * n + 1] = alive[3 * n + 5] = 0;
+  alive[4 * n + 0] = alive[4 * n + 1] = alive[4 * n + 2] = 0;
+  int32_t res[5];
+  nxec::MixedPlan plan;
+  nxec::mixed_plan(nxec::MixedMode::Recover, n, k, alive, 5, res, &plan);
+  const int32_t want_res[5] = {0, 1, 1, 2, NXEC_RECOVER_LOST};
+  EXPECT(std::memcmp(res, want_res, sizeof res) == 0, "hand tables: verdicts");
+  EXPECT(plan.plans.size() == 2 && plan.nsegments == 2 && plan.nstripes_planned == 3, "hand tables: 2 plans, 2 segments");
+  std::vector<nxec::MixedSeg> sg;
+  std::vector<uint32_t> order, seg_of;
+  nxec::mixed_tables(plan, k, cs, cs, false, sg, order, seg_of);
+  EXPECT(order == std::vector<uint32_t>({1, 2, 3}) && seg_of == std::vector<uint32_t>({0, 0, 1}), "hand tables: items");
+  if (sg.size() != 2) {
+    EXPECT(false, "hand tables: %zu segments", sg.size());
+    return;
+  }
+  nxec::MixedSeg want[2];
+  std::memset(want, 0, sizeof want);
+  for (nxec::MixedSeg &g : want)
+    for (uint32_t &c : g.copy_off) c = nxec::kNoCopy;
+  want[0].rows = 1;
+  want[0].dst_off[0] = 0;
+  const uint32_t src0[4] = {64, 128, 192, 256}, src1[4] = {0, 128, 192, 256};
+  const uint8_t coef0[4] = {1, 1, 1, 1}, coef1[8] = {1, 1, 1, 1, 3, 6, 10, 2};
+  std::memcpy(want[0].src_off, src0, sizeof src0);
+  std::memcpy(want[0].coef, coef0, sizeof coef0);
+  want[1].rows = 2;
+  want[1].dst_off[0] = 64;
+  want[1].dst_off[1] = 320;
+  std::memcpy(want[1].src_off, src1, sizeof src1);
+  std::memcpy(want[1].coef, coef1, sizeof coef1);
+  for (int g = 0; g < 2; g++) {
+    EXPECT(sg[g].rows == want[g].rows, "hand tables: rows of segment %d: %u", g, sg[g].rows);
+    EXPECT(std::memcmp(sg[g].dst_off, want[g].dst_off, sizeof want[g].dst_off) == 0, "hand tables: dst_off of segment %d", g);
+    EXPECT(std::memcmp(sg[g].src_off, want[g].src_off, sizeof want[g].src_off) == 0, "hand tables: src_off of segment %d", g);
+    EXPECT(std::memcmp(sg[g].coef, want[g].coef, sizeof want[g].coef) == 0, "hand tables: coef of segment %d", g);
+    for (int j = 0; j < nxec::kMaxRaggedK; j++)
+      EXPECT(sg[g].copy_off[j] == nxec::kNoCopy, "hand tables: copy_off[%d] of segment %d is set", j, g);
+  }
+}
+
 }  // namespace
 
 int main() {
+  hand_tables();
   enumerate(6, 4, 21, 0);
   enumerate(14, 10, 1470, 0);
   enumerate(10, 4, 847, 0);

@@ -5,7 +5,7 @@ nxec_rs_decode_stripes) and against nxec_rs_recover_mixed_plan, the argument
 validation of the plan call, of nxec_rs_decode_stripes_mixed and of
 nxec_decode_object_mixed, and the two stand-alone C++ programs
 (tests/cpp/decode_mixed_plan_test.cc under ASan + UBSan,
-tests/cpp/decode_mixed_registry_test.cc against libnxec).
+tests/cpp/mixed_registry_test.cc against libnxec).
 
 Every erasure set of 0..n-k chunks is one stripe.
 """
@@ -240,6 +240,6 @@ def test_standalone_planner_program_under_sanitizers():
 
 
 def test_every_decode_mixed_kernel_is_prepared():
-    """tests/cpp/decode_mixed_registry_test.cc: every k_decode_mixed instantiation is in the per-device
+    """tests/cpp/mixed_registry_test.cc: every k_decode_mixed instantiation is in the per-device
     preparation list with at least the LDS its launch asks for."""
-    run_program("decode_mixed_registry_test", "decode_mixed_registry_test ok", sanitized=False)
+    run_program("mixed_registry_test", "mixed_registry_test ok", sanitized=False)

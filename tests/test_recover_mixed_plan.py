@@ -3,7 +3,7 @@ plan counters of nxec_rs_recover_mixed_plan against a brute-force evaluation
 with nxec_rs_plan, the argument validation of the plan call and of
 nxec_rs_recover_stripes_mixed, and the two stand-alone C++ programs
 (tests/cpp/recover_mixed_plan_test.cc under ASan + UBSan,
-tests/cpp/recover_mixed_registry_test.cc against libnxec).
+tests/cpp/mixed_registry_test.cc against libnxec).
 
 Every erasure set of 1..n-k chunks is one stripe.  The pinned counts are the
 number of such sets, sum_{e=1..n-k} C(n, e), and the number of them whose first
@@ -181,6 +181,6 @@ def test_standalone_planner_program_under_sanitizers():
 
 
 def test_every_mixed_kernel_is_prepared():
-    """tests/cpp/recover_mixed_registry_test.cc: for k = 1..19 the kernel the mixed launch picks is in the
+    """tests/cpp/mixed_registry_test.cc: for k = 1..19 the kernel the mixed launch picks is in the
     per-device preparation list with at least the LDS the launch asks for."""
-    run_program("recover_mixed_registry_test", "recover_mixed_registry_test ok", sanitized=False)
+    run_program("mixed_registry_test", "mixed_registry_test ok", sanitized=False)
