@@ -11,9 +11,12 @@ An instantiation is named by a tuple:
   ("k_mul_vec_dyn", gather)                  ("k_mul_bytes", gather)
   ("k_scrub_vec", kd, rows, full)            ("k_mul_ragged", k)
   ("k_mul_md5", k, hsrc)                     ("k_gather_md5", k, hsrc)
-  ("k_files_md5", k, mask, tstore)
-k_mul_list, k_scrub_bytes and the plain MD5 kernels are not templates over k;
-their launches are recorded and checked per case but are not part of the set.
+  ("k_files_md5", k, mask, tstore)           ("k_mul_mixed", k)
+  ("k_decode_mixed", k)                      ("k_update_vec", r)
+k_mul_list, k_scrub_bytes, k_update_bytes and the plain MD5 kernels are not
+templates over k; their launches are recorded and checked per case but are not
+part of the set.  k_update_vec takes k at run time, but k sizes its LDS and the
+updated chunk's index picks the table, so group (h) still runs every k.
 
 The constants below mirror nexoedge_amd/csrc (the CPU test reads the sources
 and fails when one moves).
@@ -42,7 +45,9 @@ SCRUB_MAX_SRC = 20        # kScrubMaxSrc
 MUL_MD5_MAX_K = 20        # kEncMd5MaxK
 GATHER_MD5_MAX_K = 16     # kGatherMd5MaxK
 FILES_MD5_MAX_K = 16      # kFilesMd5MaxK
+UPDATE_MAX_K16 = 9        # kUpdateMaxK16
 SENTINEL = 0xEE
+MIXED_LOST = -1           # NXEC_RECOVER_LOST
 
 SOURCE_CONSTANTS = {  # name in the sources -> (file, value here)
     "kBlock": ("nxec_kernels.hip", KBLOCK),
@@ -52,6 +57,7 @@ SOURCE_CONSTANTS = {  # name in the sources -> (file, value here)
     "kPermPrefetchMaxK": ("nxec_kernels.hip", PERM_PREFETCH_MAX_K),
     "kPermMaxK": ("nxec_kernels.hip", PERM_MAX_K),
     "kRingBytes": ("nxec_kernels.hip", RING_BYTES),
+    "kUpdateMaxK16": ("nxec_kernels.hip", UPDATE_MAX_K16),
     "kMaxRowsPerPass": ("nxec_internal.h", MAX_ROWS),
     "kMaxRaggedK": ("nxec_internal.h", RAGGED_MAX_K),
     "kScrubMaxK": ("nxec_internal.h", SCRUB_MAX_K),
@@ -157,9 +163,67 @@ def scrub_launches(kd, rows, length, chunk_stride):
     return out
 
 
+def mixed_launch(k, decode):
+    """The one launch of nxec_rs_recover_stripes_mixed / nxec_rs_decode_stripes_mixed on an aligned batch with
+    k <= RAGGED_MAX_K (launch_mixed): `rows` is always MAX_ROWS, the segment records carry the real counts."""
+    assert 1 <= k <= RAGGED_MAX_K
+    tpg = tiles_per_grab(k, 0, k) if decode else tiles_per_grab(k, MAX_ROWS)
+    return dict(family="k_decode_mixed" if decode else "k_mul_mixed", k=k, rows=MAX_ROWS, r=default_r(k),
+                pf=int(k <= PREFETCH_MAX_K_COPY), q=1, tpg=tpg)
+
+
+def update_launches(n, k, rounds):
+    """The launches of nxec_rs_update_stripes(n, k) in order; `rounds` lists (vector tiles, updates, byte items)
+    per round.  Per round and per pass of <= MAX_ROWS parity rows: launch_update_vec, then launch_update_bytes
+    (each left out when it has no work); only the last pass stores the new data."""
+    out = []
+    m = n - k
+    passes = max(1, -(-m // MAX_ROWS))
+    for rnd, (tiles, updates, items) in enumerate(rounds):
+        for p in range(passes):
+            rows = min(MAX_ROWS, m - p * MAX_ROWS)
+            last = int(p == passes - 1)
+            where = {"round": rnd, "pass": p, "last": last}
+            if tiles > 0:
+                assert k <= RAGGED_MAX_K
+                out.append(dict(family="k_update_vec", k=k, rows=rows, r=default_r(k), pf=1, q=1,
+                                tpg=tiles_per_grab(2 + last, 2 * rows), tiles=tiles, updates=updates, **where))
+            if items > 0:
+                out.append(dict(family="k_update_bytes", k=k, rows=rows, r=1, items=items, **where))
+    return out
+
+
+def update_counters(n, k, cs, ss, length, addr, ups):
+    """(rounds, vector tiles, byte items) of a valid update list [(stripe, chunk, offset, length, d_new)],
+    evaluated update by update: what nxec_rs_update_plan counts (nxec_update_host.cpp)."""
+    live = [u for u in ups if u[3] > 0]
+    # rounds: the most updates over one column of one stripe (sweep over the range ends)
+    rounds = 0
+    for stripe in {u[0] for u in live}:
+        ev = sorted([(u[2], 1) for u in live if u[0] == stripe] + [(u[2] + u[3], -1) for u in live if u[0] == stripe])
+        depth = 0
+        for _, d in ev:  # at equal columns the -1 sorts first: adjacent ranges do not stack
+            depth += d
+            rounds = max(rounds, depth)
+    vec_layout = k <= RAGGED_MAX_K and addr % 16 == 0 and cs % 16 == 0 and ss % 16 == 0
+    tiles = items = 0
+    for _, _, off, ln, p in live:
+        b0, b1 = rup(off), (off + ln) // 16 * 16
+        if vec_layout and b0 < b1 and (p + b0 - off) % 16 == 0:
+            tiles += -(-((b1 - b0) // 16) // KBLOCK)
+            items += (off < b0) + (b1 < off + ln)
+        else:
+            items += 1
+    return rounds, tiles, items
+
+
 def inst_of(rec):
     """Launch record (dict) -> instantiation tuple, or None for a kernel that is not a template over k."""
     f = rec["family"]
+    if f in ("k_mul_mixed", "k_decode_mixed"):
+        return (f, rec["k"])
+    if f == "k_update_vec":
+        return (f, rec["r"])
     if f == "k_mul_vec":
         return (f, rec["k"], rec["r"], rec["gather"], rec["copy"], rec["full"])
     if f == "k_mul_perm":
@@ -210,6 +274,10 @@ def expected_instantiations():
                 s.add(("k_scrub_vec", kd, rows, full))
     for k in range(1, RAGGED_MAX_K + 1):
         s.add(("k_mul_ragged", k))
+        s.add(("k_mul_mixed", k))
+        s.add(("k_decode_mixed", k))
+    for r in (16, 8):
+        s.add(("k_update_vec", r))
     for k in range(1, GATHER_MD5_MAX_K + 1):
         for hsrc in (0, 1):
             s.add(("k_gather_md5", k, hsrc))
@@ -340,9 +408,165 @@ def e_p(k):
     return 1 if k % 2 else 4  # alternates between 1 and 4
 
 
+# ------------------------------------------- the mixed plan, in Python
+def sentinel_bytes(nbytes):
+    """A position-dependent fill of period 251 (a prime: no chunk or stripe stride here is a multiple)."""
+    return np.resize(((np.arange(251, dtype=np.uint32) * 7 + 0x5A) % 251).astype(np.uint8), nbytes)
+
+
+def mixed_model(n, k, sets, decode):
+    """What mixed_plan and mixed_tables (nxec_mixed_host.cpp) make of one erased set per stripe, for sets whose
+    first k alive chunks invert (the CPU test checks that with the oracle; SINGULAR is not modelled).
+    Recover keys a plan by the erased set, rebuilds all of it and leaves a clean stripe unplanned; Decode keys
+    a plan by the first k alive ids, rebuilds the lost data chunks and plans a clean stripe as a pure copy.
+    More than n - k erasures: MIXED_LOST.  Plans become segments of <= MAX_ROWS rows in first-appearance
+    order (a plan without rows is one segment of 0 rows); items run by segment, then ascending stripe.
+    Returns dict(verdict per stripe, plans, segs, stripes planned, seg_rows per segment, order: stripe per item)."""
+    index, plan_rows, plan_stripes, verdict = {}, [], [], []
+    for s, e in enumerate(sets):
+        e = sorted(set(e))
+        assert all(0 <= c < n for c in e)
+        if len(e) > n - k:
+            verdict.append(MIXED_LOST)
+            continue
+        if decode:
+            key = tuple([c for c in range(n) if c not in e][:k])
+            rows = sum(c < k for c in e)
+        else:
+            key, rows = tuple(e), len(e)
+            if not e:
+                verdict.append(0)
+                continue
+        if key not in index:
+            index[key] = len(plan_rows)
+            plan_rows.append(rows)
+            plan_stripes.append([])
+        assert plan_rows[index[key]] == rows
+        plan_stripes[index[key]].append(s)
+        verdict.append(rows)
+    seg_rows, order = [], []
+    for rows, stripes in zip(plan_rows, plan_stripes):
+        for r0 in range(0, max(rows, 1), MAX_ROWS):
+            seg_rows.append(min(MAX_ROWS, rows - r0))
+            order += stripes
+    return dict(verdict=verdict, plans=len(plan_rows), segs=len(seg_rows), stripes=sum(map(len, plan_stripes)),
+                seg_rows=seg_rows, order=order)
+
+
+def first_alive(n, k, e):
+    return [c for c in range(n) if c not in e][:k]
+
+
+MIXED_MODES = ("recover", "decode")
+MIXED_EXTRA = 6  # groups (f) and (g): n = k + 6, so plans of 5 and 6 erasures (two segments) exist for every k
+
+
+def three_of(k):
+    """Chunk 0, chunk 1 and the first parity chunk (k = 1 has no chunk 1: two ids)."""
+    return tuple(sorted({0, min(1, k - 1), k}))
+
+
+# ---------------------------------------- (f) every mixed instantiation
+F_LEN = TILE + 48             # one complete tile and a tile of 3 vectors
+F_STRIDE = F_LEN + 48         # source chunk stride; the stripe stride is one chunk more than n chunks
+F_OUT_STRIDE = F_LEN + 32     # decode: output chunk stride; the stripe stride is one chunk more than k chunks
+
+
+def f_cases():
+    return [(mode, k) for mode in MIXED_MODES for k in range(1, RAGGED_MAX_K + 1)]
+
+
+def f_lost(k):
+    return tuple(range(MIXED_EXTRA + 1))
+
+
+def f_sets(k, decode):
+    """One erased set per stripe.  The first plans to appear have 4, 1, 2 and 3 rows (as far as k allows:
+    the decode's rows are the lost data chunks, at most k), so a 4-row segment is followed by each shorter
+    one; then every chunk as the only target, pairs and triples across the data/parity border, full sets of
+    4, plans of 5 and 6 (two segments), the one LOST stripe, and a clean stripe at each end."""
+    n = k + MIXED_EXTRA
+    two = three_of(k) if decode else (0, n - 1)  # two lost data chunks / two erased chunks
+    sets = [(), tuple(range(4)), (0,), two, tuple(range(3))]
+    sets += [(c,) for c in range(1, n)]
+    sets += [(0, n - 1), (k - 1, k), three_of(k), tuple(range(n - 4, n)), tuple(range(0, n, 2))[:4], tuple(range(5)),
+             f_lost(k), tuple(range(n - 6, n)), tuple(range(k - 1, k + 5)), ()]
+    return sets
+
+
+def f_row_sequence(k, decode):
+    """The rows of the segments that the first plans of f_sets make: 4, 1, 2, 3, but a decode has at most k
+    lost data chunks (and at k = 2 the 2-row and the 3-row set are the same set)."""
+    if not decode:
+        return [4, 1, 2, 3]
+    return [min(4, k), 1, min(2, k)] + ([3] if k >= 3 else [])
+
+
+# ------------------------------------------- (g) mixed steady state
+G_KS = (1, PREFETCH_MAX_K_COPY, UPDATE_MAX_K16, RAGGED_MAX_K)  # most tiles per grab, last prefetch, largest table, widest
+G_CS = TILE  # one tile per chunk, packed
+
+
+def g_cases():
+    return [(mode, k) for mode in MIXED_MODES for k in G_KS]
+
+
+def g_sets(k):
+    """The patterns stripe s % len takes, for both modes: 4, 1, 0, 6, 2, 3, 4, 5 and 3 erased chunks.  Recover:
+    a 4-row segment, then 1 row; 6 and 5 erasures are plans of two segments (4 + 2, 4 + 1); the clean stripes
+    are unplanned.  Decode (rows = lost data chunks): 4, 1, then the clean plan, a pure-copy segment between
+    coded ones that the parity-only set joins; range(5) is its plan of two segments where k >= 5."""
+    n = k + MIXED_EXTRA
+    return [tuple(range(4)), (k - 1,), (), tuple(range(k - 1, k + 5)), (0, n - 1), three_of(k), tuple(range(n - 4, n)),
+            tuple(range(5)), tuple(range(3))]
+
+
+def g_stripes(k, decode, cus):
+    """4 * cus * T stripes of one tile: at least half of all tiles come from published grabs."""
+    return 4 * cus * mixed_launch(k, decode)["tpg"]
+
+
+def g_seed(k, decode):
+    return 99000 + 10 * k + int(decode)
+
+
+# ------------------------------------------------- (h) update sweep
+H_ROWS = (4, 6, 1, 2, 5, 3)
+H_OFF, H_BYTES = 3, TILE + 40  # a 13-byte head, 1025 vectors (a full tile and one more), an 11-byte tail
+
+
+def h_p(k):
+    return H_ROWS[(k - 1) % len(H_ROWS)]
+
+
+def h_specs(k):
+    """(stripe, chunk, offset, length): stripe s < k updates chunk s; stripe k stays untouched."""
+    return [(s, s, H_OFF, H_BYTES) for s in range(k)]
+
+
+def h_new_offset(i):
+    """Where update i's new bytes start in the d_new buffer: 64-byte slots, aligned like the chunk offset."""
+    return 64 + i * rup(H_BYTES + 64, 64) + H_OFF % 16
+
+
+def h_plan(k, batch_addr=0, new_addr=0):
+    """The launches of the (h) case of k; the addresses only matter modulo 16."""
+    n, cs = k + h_p(k), F_STRIDE
+    ups = [(s, c, off, ln, new_addr + h_new_offset(i)) for i, (s, c, off, ln) in enumerate(h_specs(k))]
+    rounds, tiles, items = update_counters(n, k, cs, n * cs, F_LEN, batch_addr, ups)
+    assert rounds == 1
+    return update_launches(n, k, [(tiles, len(ups), items)])
+
+
 def all_cases():
     """Every (group, instantiations the case's plan names) pair that can be planned without a device."""
     out = []
+    for mode, k in f_cases():
+        out.append(("f", [inst_of(mixed_launch(k, mode == "decode"))]))
+    for mode, k in g_cases():
+        out.append(("g", [inst_of(mixed_launch(k, mode == "decode"))]))
+    for k in range(1, RAGGED_MAX_K + 1):
+        out.append(("h", [i for i in map(inst_of, h_plan(k)) if i is not None]))
     for c in a_cases():
         out.append(("a", [inst_of(r) for r in a_plan(c)]))
     for c in b_cases():

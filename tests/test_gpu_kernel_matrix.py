@@ -16,7 +16,16 @@ whole module to have run.
 Groups: (a) every multiply instantiation, (b) the work queue's steady state
 (workgroups consuming published grabs) for every queued instantiation, (c) the
 stripe-group tile order, (d) scrub detect for all 64 (KD, ROWS), (e) the fused
-MD5 families and the ragged launch.
+MD5 families and the ragged launch, (f) every mixed recover and mixed decode
+instantiation on a batch whose stripes lost different chunks, (g) the mixed
+kernels' steady state, where a workgroup's next tile is nearly always of
+another segment than the one whose tables are resident, (h) the update
+kernels at every k, every chunk index the updated one once.
+
+In (f), (g) and (h) the batches are built on the host: data random (or the
+fill stream), parity from oracle.rs_encode (oracle.simd_encode in (g)); the
+expected verdicts and the launch's segment and stripe counts come from the
+Python model of the plan in kernel_matrix.py, never from a library call.
 """
 import ctypes as C
 import hashlib
@@ -245,12 +254,13 @@ def test_c_stripe_group_tile_order(gpu_ctx, ns):
 
 
 # --------------------------------------------------------------------- (d)
-def scrub_batch(n, k, length, stride, ns, seed):
-    """Host image [ns][n][stride] of oracle-encoded stripes (random bytes in the stride padding)."""
+def scrub_batch(n, k, length, stride, ns, seed, slots=None):
+    """Host image [ns][slots or n][stride] of oracle-encoded stripes (random bytes in the stride padding and
+    in the slots past chunk n - 1)."""
     rng = np.random.default_rng(seed)
-    img = rng.integers(0, 256, size=(ns, n, stride), dtype=np.uint8)
+    img = rng.integers(0, 256, size=(ns, slots or n, stride), dtype=np.uint8)
     for s in range(ns):
-        img[s, :, :length] = oracle.rs_encode(n, k, img[s, :k, :length].reshape(-1), length)
+        img[s, :n, :length] = oracle.rs_encode(n, k, img[s, :k, :length].reshape(-1), length)
     return img
 
 
@@ -525,6 +535,181 @@ def test_e_ragged_launch(gpu_ctx, k):
             for r0 in range(0, p, km.MAX_ROWS)]
     assert len(rag) == len(want) and all(km.matches(r, w) for r, w in zip(rag, want)), (rag, want)
     assert bool(lst) == (k % 2 == 0), recs  # misaligned objects: their full stripes through the list kernel
+
+
+# --------------------------------------------------------------- (f), (g)
+def first_difference(got, want, ns, tag, wrong=None):
+    """Whole-image comparison of two [ns][...] arrays: fails naming the wrong stripes and the first differing
+    byte, or, with a list for `wrong`, stores the wrong stripes there instead."""
+    if wrong is None and got.shape == want.shape and got.nbytes % 8 == 0:  # the usual outcome, eight bytes at a time
+        if np.array_equal(got.reshape(-1).view(np.uint64), want.reshape(-1).view(np.uint64)):
+            return
+    ne = (got != want).reshape(ns, -1)
+    bad = np.flatnonzero(ne.any(axis=1))
+    if wrong is not None:
+        wrong += bad.tolist()
+    if wrong is not None or bad.size == 0:
+        return
+    s = int(bad[0])
+    pytest.fail(f"{tag}: {bad.size} wrong stripes {bad[:8].tolist()}, first differing byte in stripe {s} at stripe "
+                f"byte {int(np.flatnonzero(ne[s])[0])} (stripe shape {got.shape[1:]})")
+
+
+def run_mixed(ctx, decode, n, k, truth, length, sets, out_slots=None, out_stride=None, cus=None, before_launch=None,
+              wrong=None):
+    """One nxec_rs_recover_stripes_mixed / nxec_rs_decode_stripes_mixed call over the host image `truth`
+    [ns][slots >= n][chunk stride] of oracle-encoded stripes, stripe s erased at sets[s].  The image is
+    uploaded and the erased chunks alone are overwritten on the device, with garbage that differs from the
+    truth in every byte.  Recover: the whole buffer comes back as the truth, but a stripe with a negative
+    verdict keeps its garbage.  Decode: the output, prefilled with km.sentinel_bytes, holds the original data
+    chunks of every stripe with a verdict >= 0 and the sentinel everywhere else; the source is unchanged.
+    Verdicts, segments and stripes are the Python model's (km.mixed_model), the one launch km.mixed_launch's.
+    `truth` is used up: the garbage the device must still hold is written into it before the comparison."""
+    ns, slots, cs = truth.shape
+    mode = km.MIXED_MODES[decode]
+    model = km.mixed_model(n, k, sets, decode)
+    verdict = np.array(model["verdict"])
+    alive = np.ones((ns, n), dtype=np.uint8)
+    mask = np.random.default_rng(31 * k + decode).integers(1, 256, size=length, dtype=np.uint8)  # no zero byte
+    by_set = {}
+    for s, e in enumerate(sets):
+        by_set.setdefault(tuple(e), []).append(s)
+    src = up(truth)
+    junk = {}  # erased set -> the garbage of its stripes' erased chunks, [stripes][chunks][length]
+    for e, idx in by_set.items():
+        if e:
+            alive[np.ix_(idx, e)] = 0
+            junk[e] = j = truth[np.ix_(idx, e)][:, :, :length] ^ mask
+            for a, s in enumerate(idx):
+                for b, c in enumerate(e):  # one wait for all of them, below
+                    nxec.check(lib.nxec_memcpy_h2d(src.addr((s * slots + c) * cs),
+                                                   C.c_void_p(j.ctypes.data + (a * len(e) + b) * length), length, None), "h2d")
+    nxec.check(lib.nxec_stream_sync(None), "sync")
+
+    def keep_garbage(keep):  # keep: one bool per stripe
+        for e, j in junk.items():
+            idx = np.array(by_set[e])
+            sel = keep[idx]
+            for b, c in enumerate(e):
+                truth[idx[sel], c, :length] = j[sel, b]
+
+    out = None
+    if decode:
+        oslots, ocs = out_slots or k, out_stride or cs
+        blank = km.sentinel_bytes(ns * oslots * ocs).reshape(ns, oslots, ocs)
+        out = up(blank)
+    nxec.launch_log_read()
+    if before_launch:
+        before_launch()
+    if decode:
+        res = ctx.rs_decode_mixed(n, k, alive, src.ptr, cs, slots * cs, out.ptr, ocs, oslots * ocs, length, ns)
+    else:
+        res = ctx.rs_recover_mixed(n, k, alive, src.ptr, cs, slots * cs, length, ns)
+    ctx.sync()
+    recs = note(nxec.launch_log_read())
+    got = src.download().reshape(truth.shape)
+    got_out = out.download().reshape(blank.shape) if decode else None
+    src.free()
+    if decode:
+        out.free()
+    assert res.tolist() == model["verdict"], (mode, k, res.tolist(), model["verdict"])
+    plan = dict(km.mixed_launch(k, decode), segs=model["segs"], stripes=model["stripes"])
+    assert len(recs) == 1 and km.matches(recs[0], plan), (recs, plan)
+    if cus is not None:  # one workgroup per CU and >= 4 grabs each, or the case does not reach the steady state
+        m = recs[0]
+        assert m["grid"] == cus and ns * (-(-length // km.TILE)) >= 4 * m["grid"] * m["tpg"], (m, ns)
+    if decode:
+        np.copyto(blank[:, :k, :length], truth[:, :k, :length], where=(verdict >= 0)[:, None, None])
+        first_difference(got_out, blank, ns, (mode, k, "output"), wrong)
+        keep_garbage(np.ones(ns, dtype=bool))
+        first_difference(got, truth, ns, (mode, k, "the source was written"))
+    else:
+        keep_garbage(verdict < 0)  # a LOST stripe is left as it was
+        first_difference(got, truth, ns, (mode, k, "batch"), wrong)
+
+
+@pytest.mark.parametrize("mode,k", km.f_cases(), ids=lambda v: str(v))
+def test_f_every_mixed_instantiation(gpu_ctx, mode, k):
+    """k_mul_mixed<K> / k_decode_mixed<K> for every K: a complete tile and a tile of 3 vectors, padded chunk
+    and stripe strides with random bytes in the padding, every chunk the only target once, segments of 4, 1,
+    2 and 3 rows in a row, plans of two segments, one LOST stripe."""
+    decode = mode == "decode"
+    n = k + km.MIXED_EXTRA
+    sets = km.f_sets(k, decode)
+    truth = scrub_batch(n, k, km.F_LEN, km.F_STRIDE, len(sets), 1200 + 10 * k + decode, slots=n + 1)
+    run_mixed(gpu_ctx, decode, n, k, truth, km.F_LEN, sets, out_slots=k + 1, out_stride=km.F_OUT_STRIDE)
+
+
+def g_batch(k, decode, cus):
+    """(n, truth [ns][n][G_CS], sets).  The truth as host_encode makes it, but in one [ns][n] image: the data
+    chunks of stripe s are the fill stream from byte s * k * cs on (oracle.fill_bytes_at), its parity is the
+    generator's parity rows x those chunks (oracle.simd_encode); stripe ranges run on a few threads."""
+    from concurrent.futures import ThreadPoolExecutor
+    n, cs, seed = k + km.MIXED_EXTRA, km.G_CS, km.g_seed(k, decode)
+    ns = km.g_stripes(k, decode, cus)
+    enc = oracle.gen_rs_matrix(n, k)[k:]
+    truth = np.empty((ns, n, cs), dtype=np.uint8)
+
+    def work(lo):
+        for s in range(lo, min(lo + step, ns)):
+            oracle.fill_bytes_at(truth[s, :k].reshape(-1), seed, s * k * cs)
+            oracle.simd_encode(enc, [truth[s, j] for j in range(k)], [truth[s, k + r] for r in range(n - k)])
+
+    step = max(1, -(-ns // 16))
+    with ThreadPoolExecutor(8) as ex:
+        list(ex.map(work, range(0, ns, step)))
+    pats = km.g_sets(k)
+    return n, truth, [pats[s % len(pats)] for s in range(ns)]
+
+
+@pytest.mark.parametrize("mode,k", km.g_cases(), ids=lambda v: str(v))
+def test_g_mixed_steady_state(gpu_ctx, mode, k):
+    """>= 4 * cus * T one-tile stripes whose patterns interleave (km.g_sets): most tiles come from published
+    grabs, and a workgroup's next tile is nearly always of another segment than the resident one -- under
+    prefetch (k <= 8), after a 4-row segment, in the second segment of a plan, across the decode's pure copies."""
+    decode = mode == "decode"
+    cus = cus_of(gpu_ctx)
+    n, truth, sets = g_batch(k, decode, cus)
+    run_mixed(gpu_ctx, decode, n, k, truth, km.G_CS, sets, cus=cus)
+
+
+def test_g_checker_sees_skipped_tiles(gpu_ctx):
+    """Negative control: a launch whose queue counter starts at 5 (nxec_debug_poison_next_queue_slot) never
+    runs items 0..4 (one tile each, one tile per grab at k = 9), and the steady-state check reports exactly
+    their stripes."""
+    k, cus = km.UPDATE_MAX_K16, cus_of(gpu_ctx)
+    assert km.mixed_launch(k, False)["tpg"] == 1
+    n, truth, sets = g_batch(k, False, cus)
+    wrong = []
+    run_mixed(gpu_ctx, False, n, k, truth, km.G_CS, sets, cus=cus, wrong=wrong,
+              before_launch=lambda: nxec.check(lib.nxec_debug_poison_next_queue_slot(5), "poison"))
+    assert wrong == sorted(km.mixed_model(n, k, sets, False)["order"][:5]) and len(set(wrong)) == 5
+
+
+# --------------------------------------------------------------------- (h)
+@pytest.mark.parametrize("k", range(1, km.RAGGED_MAX_K + 1))
+def test_h_update_every_k(gpu_ctx, k):
+    """k_update_vec<16> (k <= 9) and <8> with the LDS of every k: stripe s updates chunk s, so every table
+    of the k, the last one right under the queue ring included, multiplies once; 1 to 6 parity rows."""
+    n, length, cs, ns = k + km.h_p(k), km.F_LEN, km.F_STRIDE, k + 1
+    img = scrub_batch(n, k, length, cs, ns, 1300 + k)
+    specs = km.h_specs(k)
+    new = np.random.default_rng(1400 + k).integers(0, 256, size=km.h_new_offset(len(specs)), dtype=np.uint8)
+    want = img.copy()
+    for i, (s, c, off, ln) in enumerate(specs):
+        want[s, c, off: off + ln] = new[km.h_new_offset(i): km.h_new_offset(i) + ln]
+        want[s, :, :length] = oracle.rs_encode(n, k, want[s, :k, :length].reshape(-1), length)
+    buf, nb = up(img), up(new)
+    nxec.launch_log_read()
+    gpu_ctx.rs_update(n, k, buf.ptr, cs, n * cs, length, ns,
+                      [(s, c, off, ln, nb.ptr + km.h_new_offset(i)) for i, (s, c, off, ln) in enumerate(specs)])
+    gpu_ctx.sync()
+    take(km.h_plan(k, buf.ptr, nb.ptr))
+    got, new_after = buf.download().reshape(img.shape), nb.download()
+    buf.free()
+    nb.free()
+    first_difference(got, want, ns, ("update", k))
+    assert np.array_equal(new_after, new), (k, "d_new was written")
 
 
 # ---------------------------------------------------------------- complete

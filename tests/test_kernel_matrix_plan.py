@@ -46,8 +46,9 @@ def test_expected_set_has_the_size_the_tables_imply():
     # k_files_md5<1, MASK, !TSTORE> is unreachable: a one-chunk last stripe has no partial chunk to mask
     assert km.UNREACHABLE == {("k_files_md5", 1, 1, 0)}
     assert count == {"k_mul_vec": 120, "k_mul_perm": 25, "k_mul_vec_dyn": 2, "k_mul_bytes": 2, "k_scrub_vec": 128,
-                     "k_mul_ragged": 19, "k_mul_md5": 40, "k_gather_md5": 32, "k_files_md5": 48 - 1}
-    assert len(want) == 120 + 25 + 2 + 2 + 128 + 19 + 40 + 32 + 48 - len(km.UNREACHABLE)
+                     "k_mul_ragged": 19, "k_mul_md5": 40, "k_gather_md5": 32, "k_files_md5": 48 - 1,
+                     "k_mul_mixed": 19, "k_decode_mixed": 19, "k_update_vec": 2}
+    assert len(want) == 120 + 25 + 2 + 2 + 128 + 19 + 40 + 32 + 48 - len(km.UNREACHABLE) + 19 + 19 + 2 == 455
 
 
 def test_every_case_maps_into_the_expected_set_and_covers_it():
@@ -137,6 +138,176 @@ def test_scrub_flips_change_the_oracle_syndrome(kd, rows):
             assert any(syn), (c, pos)
             chunk, _ = nxec.syndrome_locate(n, kd, syn)
             assert chunk == (c if rows >= 2 else nxec.SCRUB_UNLOCATED), (c, pos, syn)
+
+
+# ------------------------------------------------- groups (f), (g) and (h)
+def alive_of(n, sets):
+    a = np.ones((len(sets), n), dtype=np.uint8)
+    for s, e in enumerate(sets):
+        a[s, list(e)] = 0
+    return a
+
+
+def check_sets(n, k, sets, decode, lost=()):
+    """Every stripe but the placed LOST ones is decodable under the oracle's arithmetic (so none is left out
+    of the GPU comparison), and the Python plan model agrees with the library's host planner."""
+    enc = oracle.gen_rs_matrix(n, k)
+    for s, e in enumerate(sets):
+        if s in lost:
+            assert len(set(e)) > n - k
+            continue
+        assert len(set(e)) == len(e) <= n - k, (k, e)
+        rc, _ = oracle.invert_matrix(enc[km.first_alive(n, k, e)])
+        assert rc == 0, (n, k, e, "the first k alive rows of the generator do not invert")
+    model = km.mixed_model(n, k, sets, decode)
+    plan = (nxec.rs_decode_mixed_plan if decode else nxec.rs_recover_mixed_plan)(n, k, alive_of(n, sets))
+    assert plan[0].tolist() == model["verdict"], (n, k, decode)
+    assert plan[1:] == (model["plans"], model["segs"], model["stripes"]), (n, k, decode, plan[1:], model)
+    assert [s for s, v in enumerate(model["verdict"]) if v < 0] == sorted(lost)
+    assert len(model["order"]) >= model["stripes"] == len(set(model["order"]))
+    return model
+
+
+def holds(seq, sub):
+    return any(seq[i: i + len(sub)] == sub for i in range(len(seq) - len(sub) + 1))
+
+
+def test_mixed_model_constants_and_launch_plan():
+    assert km.MIXED_LOST == nxec.RECOVER_LOST
+    assert km.MAX_ROWS + 2 == km.MIXED_EXTRA  # plans of 5 and 6 erasures are the two-segment ones
+    for k in range(1, km.RAGGED_MAX_K + 1):
+        rec, dec = km.mixed_launch(k, False), km.mixed_launch(k, True)
+        assert (rec["family"], dec["family"]) == ("k_mul_mixed", "k_decode_mixed")
+        assert rec["rows"] == dec["rows"] == 4 and rec["q"] == dec["q"] == 1 and "full" not in rec
+        assert rec["pf"] == dec["pf"] == int(k <= 8) and rec["r"] == dec["r"] == (16 if k <= 9 else 8)
+        assert rec["tpg"] == km.tiles_per_grab(k, 4) and dec["tpg"] == km.tiles_per_grab(k, 0, k)
+        assert km.queue_fits(k * 1024 * rec["r"])
+    assert [km.mixed_launch(k, False)["tpg"] for k in km.G_KS] == [3, 1, 1, 1]
+    assert [km.mixed_launch(k, True)["tpg"] for k in km.G_KS] == [6, 1, 1, 1]
+    # the model on a hand-made batch of (10,4): decode shares one plan between every set with equal first k alive
+    sets = [(), (9,), (0,), (0, 9), (0, 1, 2, 3, 4), (0, 1, 2, 3, 4, 5, 6)]
+    m = km.mixed_model(10, 4, sets, False)
+    assert (m["verdict"], m["plans"], m["seg_rows"]) == ([0, 1, 1, 2, 5, km.MIXED_LOST], 4, [1, 1, 2, 4, 1])
+    assert m["order"] == [1, 2, 3, 4, 4] and m["stripes"] == 4
+    m = km.mixed_model(10, 4, sets, True)
+    assert (m["verdict"], m["plans"], m["seg_rows"]) == ([0, 0, 1, 1, 4, km.MIXED_LOST], 3, [0, 1, 4])
+    assert m["order"] == [0, 1, 2, 3, 4] and m["stripes"] == 5
+
+
+@pytest.mark.parametrize("mode,k", km.f_cases())
+def test_group_f_sets(mode, k):
+    decode = mode == "decode"
+    n = k + km.MIXED_EXTRA
+    sets = km.f_sets(k, decode)
+    lost = [sets.index(km.f_lost(k))]
+    assert sets.count(km.f_lost(k)) == 1 and sets.count(()) == 2 and sets[0] == sets[-1] == ()
+    model = check_sets(n, k, sets, decode, lost)
+    # every chunk is the only erased one once; the pairs, the full sets and the two-segment plans are there
+    for e in [(c,) for c in range(n)] + [(0, n - 1), (k - 1, k), km.three_of(k), tuple(range(4)), tuple(range(n - 4, n)),
+                                         tuple(range(0, n, 2))[:4], tuple(range(5)), tuple(range(n - 6, n)),
+                                         tuple(range(k - 1, k + 5))]:
+        assert e in sets, (k, e)
+    # a 4-row segment is followed by a 1-row, a 2-row and a 3-row one (the decode's rows: lost data chunks <= k)
+    assert holds(model["seg_rows"], km.f_row_sequence(k, decode)), (mode, k, model["seg_rows"])
+    if not decode or k >= 4:
+        assert km.f_row_sequence(k, decode) == [4, 1, 2, 3]
+    if not decode or k >= 5:  # range(5) and, in place, range(n - 6, n): second segments of 1 and 2 rows
+        assert holds(model["seg_rows"], [4, 1]) and (decode or holds(model["seg_rows"], [4, 2]))
+    assert km.F_LEN % 16 == 0 and km.F_LEN // 16 == km.KBLOCK + 3
+    assert len(sets) * (n + 1) * km.F_STRIDE <= 17 << 20  # about 16 MB at the widest
+
+
+@pytest.mark.parametrize("mode,k", km.g_cases())
+def test_group_g_patterns(mode, k):
+    decode = mode == "decode"
+    n = k + km.MIXED_EXTRA
+    pats = km.g_sets(k)
+    assert len(pats) >= 6 and {4, 1, 6, 2, 3, 5} <= {len(e) for e in pats}
+    assert () in pats and tuple(range(n - 4, n)) in pats  # clean and parity-only
+    rows = check_sets(n, k, pats * 3, decode)["seg_rows"]  # repeats add stripes, not plans
+    assert rows == check_sets(n, k, pats, decode)["seg_rows"]
+    if decode:
+        # the clean plan is one pure-copy segment between coded ones; the parity-only set has the same first k
+        # alive chunks and joins it
+        z = rows.index(0)
+        assert rows.count(0) == 1 and 0 < z < len(rows) - 1 and rows[z - 1] > 0 and rows[z + 1] > 0
+        both = km.mixed_model(n, k, [(), tuple(range(n - 4, n))], True)
+        assert (both["plans"], both["seg_rows"], both["verdict"]) == (1, [0], [0, 0])
+    if decode and k < 5:
+        # at most k data chunks can be lost: k = 1 has no 4-row segment and no plan of two segments
+        assert k == 1 and set(rows) == {0, 1}
+    else:
+        assert any(a == 4 and b < 4 for a, b in zip(rows, rows[1:])), (mode, k, rows)
+        two = km.mixed_model(n, k, [tuple(range(5))], decode)
+        assert two["plans"] == 1 and two["seg_rows"] == [4, 1]
+    if not decode:
+        assert km.mixed_model(n, k, [tuple(range(k - 1, k + 5))], False)["seg_rows"] == [4, 2]
+        assert 3 in rows and 2 in rows and 1 in rows
+    for cus in (1, 64, 256, 304):
+        ns = km.g_stripes(k, decode, cus)
+        model = km.mixed_model(n, k, [pats[s % len(pats)] for s in range(ns)], decode)
+        tiles = len(model["order"]) * (km.G_CS // km.TILE)
+        assert tiles >= ns >= 4 * cus * km.mixed_launch(k, decode)["tpg"]
+
+
+def test_group_g_poisoned_items_are_the_first_pattern():
+    """The negative control skips items 0..4 of the recover at k = 9: five stripes of the first pattern."""
+    k = km.UPDATE_MAX_K16
+    pats = km.g_sets(k)
+    assert km.mixed_launch(k, False)["tpg"] == 1
+    ns = km.g_stripes(k, False, 256)
+    model = km.mixed_model(k + km.MIXED_EXTRA, k, [pats[s % len(pats)] for s in range(ns)], False)
+    assert model["order"][:5] == [0, 9, 18, 27, 36] and len(pats) == 9
+
+
+@pytest.mark.parametrize("mode", km.MIXED_MODES)
+def test_reference_alone_on_a_group_f_case(mode):
+    """The truth image of group (f) is a codeword under the oracle's own arithmetic: the inverse of the first
+    k alive rows of the generator (oracle.invert_matrix), applied with oracle.matmul, gives back the data,
+    and the generator's rows of the erased chunks applied to that give back every erased chunk."""
+    k, decode = 11, mode == "decode"
+    n, length = k + km.MIXED_EXTRA, km.F_LEN
+    enc = oracle.gen_rs_matrix(n, k)
+    rng = np.random.default_rng(4100 + decode)
+    stripe = oracle.rs_encode(n, k, rng.integers(0, 256, size=k * length, dtype=np.uint8), length)
+    assert np.array_equal(stripe[:k], np.stack(oracle.matmul(enc[:k], list(stripe[:k]))))  # systematic
+    for e in km.f_sets(k, decode):
+        if e == km.f_lost(k) or not e:
+            continue
+        ids = km.first_alive(n, k, e)
+        rc, inv = oracle.invert_matrix(enc[ids])
+        assert rc == 0
+        data = oracle.matmul(inv, [stripe[c] for c in ids])
+        assert all(np.array_equal(data[j], stripe[j]) for j in range(k)), (mode, e)
+        back = oracle.matmul(enc[list(e)], data)
+        assert all(np.array_equal(back[i], stripe[c]) for i, c in enumerate(e)), (mode, e)
+
+
+def test_group_h_table_and_plan():
+    assert sorted(km.H_ROWS) == [1, 2, 3, 4, 5, 6]
+    assert {km.h_p(k) for k in range(1, km.RAGGED_MAX_K + 1)} == set(range(1, 7))
+    assert km.h_p(km.RAGGED_MAX_K) == 4 and km.h_p(km.UPDATE_MAX_K16) == 1
+    assert km.H_OFF + km.H_BYTES <= km.F_LEN
+    batch, new = 0x7000_0000_0000, 0x7100_0000_0000  # addresses only: the planner touches no memory
+    for k in range(1, km.RAGGED_MAX_K + 1):
+        n, p, cs = k + km.h_p(k), km.h_p(k), km.F_STRIDE
+        specs = km.h_specs(k)
+        assert [(s, c) for s, c, _, _ in specs] == [(j, j) for j in range(k)]  # every chunk index once, stripe k untouched
+        ups = [(s, c, off, ln, new + km.h_new_offset(i)) for i, (s, c, off, ln) in enumerate(specs)]
+        for (_, _, _, ln, a), (_, _, _, _, b) in zip(ups, ups[1:]):
+            assert a + ln <= b  # the new bytes of two updates do not overlap
+        want = km.update_counters(n, k, cs, n * cs, km.F_LEN, batch, ups)
+        assert want == nxec.rs_update_plan(n, k, cs, n * cs, km.F_LEN, k + 1, batch, ups)
+        assert want == (1, 2 * k, 2 * k)  # a head, a full tile + a one-vector tile, a tail
+        plan = km.h_plan(k, batch, new)
+        passes = -(-p // km.MAX_ROWS)
+        assert [r["family"] for r in plan] == ["k_update_vec", "k_update_bytes"] * passes
+        assert [r["last"] for r in plan] == [0, 0, 1, 1][-2 * passes:]
+        assert [r["rows"] for r in plan[::2]] == ([4, p - 4] if p > 4 else [p])
+        for r in plan[::2]:
+            assert r["r"] == (16 if k <= km.UPDATE_MAX_K16 else 8) and (r["pf"], r["q"]) == (1, 1)
+            assert r["tpg"] == km.tiles_per_grab(2 + r["last"], 2 * r["rows"]) and r["tiles"] == 2 * k
+        assert km.queue_fits(k * 1024 * km.default_r(k))  # update_lds(k): the ring lies right above the k tables
 
 
 def test_launch_record_is_off_by_default_and_reads_empty():

@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import kernel_matrix
 from nexoedge_amd import _lib, nxec
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,27 +29,9 @@ def rup(x, m=16):
     return (x + m - 1) // m * m
 
 
-def brute(n, k, cs, ss, length, addr, ups):
-    """(rounds, vector tiles, byte items) of a valid update list, evaluated update by update."""
-    live = [u for u in ups if u[3] > 0]
-    # rounds: the most updates over one column of one stripe (sweep over the range ends)
-    rounds = 0
-    for stripe in {u[0] for u in live}:
-        ev = sorted([(u[2], 1) for u in live if u[0] == stripe] + [(u[2] + u[3], -1) for u in live if u[0] == stripe])
-        depth = 0
-        for _, d in ev:  # at equal columns the -1 sorts first: adjacent ranges do not stack
-            depth += d
-            rounds = max(rounds, depth)
-    vec_layout = k <= 19 and addr % 16 == 0 and cs % 16 == 0 and ss % 16 == 0
-    tiles = items = 0
-    for _, _, off, ln, p in live:
-        b0, b1 = rup(off), (off + ln) // 16 * 16
-        if vec_layout and b0 < b1 and (p + b0 - off) % 16 == 0:
-            tiles += -(-((b1 - b0) // 16) // TILE_VECS)
-            items += (off < b0) + (b1 < off + ln)
-        else:
-            items += 1
-    return rounds, tiles, items
+# the brute-force evaluation lives with the kernel matrix, whose update group plans its launches from it
+brute = kernel_matrix.update_counters
+assert kernel_matrix.KBLOCK == TILE_VECS and kernel_matrix.RAGGED_MAX_K == 19
 
 
 def draw(rng, k, length, ns, count, misalign=0.2):
