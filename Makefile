@@ -26,7 +26,7 @@ HDRS     := include/nxec.h $(CSRC)/nxec_internal.h $(CSRC)/nxec_runtime.h $(CSRC
 all: $(LIBDIR)/libnxec.so oracle/liboracle.so build/rs_surface_test build/isal_compat_test build/chunk_manager_flow_test \
      build/stripe_batch_test build/chunk_replay_test build/dropin_pool_test build/scrub_host_test \
      build/recover_mixed_plan_test build/decode_mixed_plan_test build/mixed_registry_test build/update_plan_test \
-     build/update_registry_test
+     build/update_registry_test build/md5_layout_test
 
 # rs.cc's ISA-L call sequence compiled against include/nxec_isal_compat.h (plain C)
 build/isal_compat_test: tests/cpp/isal_compat_test.c include/nxec_isal_compat.h $(LIBDIR)/libnxec.so
@@ -109,6 +109,15 @@ build/update_registry_test: tests/cpp/update_registry_test.cc $(LIBDIR)/libnxec.
 update-registry-test: build/update_registry_test
 	build/update_registry_test
 
+# the host rules of the fused multiply + MD5 launches (chunk_off32, mul_md5_layout_ok, mul_md5_group_cap: inline in
+# nxec_internal.h) as a stand-alone host program under ASan + UBSan, no device and no libnxec
+build/md5_layout_test: tests/cpp/md5_layout_test.cc $(HDRS)
+	@mkdir -p build
+	g++ -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
+	    -Iinclude -I$(CSRC) tests/cpp/md5_layout_test.cc -o $@
+md5-layout-test: build/md5_layout_test
+	build/md5_layout_test
+
 $(OBJDIR)/%.o: $(CSRC)/% $(HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -185,4 +194,4 @@ clean:
 	rm -rf build $(LIBDIR)/libnxec.so oracle/liboracle.so
 
 .PHONY: all ref golden clean tune tools asan ubsan tsan sanitize scrub-host-test recover-mixed-plan-test \
-        decode-mixed-plan-test mixed-registry-test update-plan-test update-registry-test
+        decode-mixed-plan-test mixed-registry-test update-plan-test update-registry-test md5-layout-test

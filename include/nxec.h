@@ -592,7 +592,10 @@ int nxec_md5_verify_chunks(nxec_ctx_t *ctx, const unsigned char *d_base, int64_t
  * 99-175) -- in one pass over the data: parity as nxec_rs_encode_stripes,
  * digests as nxec_md5_chunks (d_digests[(s*n + c)*16]).  One fused kernel
  * when n - k <= 4, k <= 20, len is a multiple of 256 and the layout is 16-byte
- * aligned; otherwise the encode, then the MD5 launch. */
+ * aligned; otherwise the encode, then the MD5 launch.  Either way the chunks
+ * of a stripe must lie within 4 GiB, (n-1)*chunk_stride + len <= 2^32 - 1, or
+ * the call gives NXEC_ERR_INVALID: the fused kernel takes exactly the layouts
+ * the two-kernel path takes, whatever len % 256 is. */
 int nxec_rs_encode_md5_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripes, int64_t chunk_stride,
                                int64_t stripe_stride, int64_t len, int64_t nstripes, unsigned char *d_digests,
                                void *stream);
@@ -603,7 +606,10 @@ int nxec_rs_encode_md5_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_s
  * out (chunk_manager.cc:1173, Chunk::computeMD5) -- in one pass.  Digest of
  * rebuilt chunk failed[r] of stripe s at d_digests[(s*nfailed + r)*16].  One
  * fused kernel when nfailed <= 4, k <= 20, len is a multiple of 256 and the
- * layout is 16-byte aligned; otherwise the recover, then the MD5 launch. */
+ * layout is 16-byte aligned; otherwise the recover, then the MD5 launch.
+ * Either way every chunk read or rebuilt must end within 4 GiB of its stripe,
+ * c*chunk_stride + len <= 2^32 - 1 (NXEC_ERR_INVALID otherwise, as
+ * nxec_rs_recover_stripes), whatever len % 256 is. */
 int nxec_rs_recover_md5_stripes(nxec_ctx_t *ctx, int n, int k, const int32_t *failed, int nfailed,
                                 unsigned char *d_stripes, int64_t chunk_stride, int64_t stripe_stride, int64_t len,
                                 int64_t nstripes, unsigned char *d_digests, void *stream);
@@ -628,7 +634,11 @@ int nxec_object_layout(int n, int k, int64_t length, int64_t max_chunk_size, int
  * be NULL when length is a multiple of k*M) receives the zero-padded data
  * chunks of the last stripe at j*last_chunk_size.  d_md5 (NULL = skip):
  * [nstripes][n][16] MD5 digests of every chunk (Chunk::computeMD5 of
- * writeFileStripe, chunk_manager.cc:175), one kernel launch. */
+ * writeFileStripe, chunk_manager.cc:175), one kernel launch.  The fused
+ * kernel runs only where the k data chunks of a stripe end within 4 GiB,
+ * (k-1)*M + M <= 2^32 - 1 (packed objects with chunks of 300 MiB and more
+ * reach this); past that the encode, then the MD5 launch, under the rule of
+ * nxec_rs_encode_stripes. */
 int nxec_encode_object(nxec_ctx_t *ctx, int n, int k, const unsigned char *d_object, int64_t length,
                        int64_t max_chunk_size, unsigned char *d_parity, unsigned char *d_tail, unsigned char *d_md5,
                        void *stream);
@@ -653,8 +663,10 @@ int nxec_decode_object_ex(nxec_ctx_t *ctx, int n, int k, const int32_t *failed, 
  * as nxec_encode_object wrote it) -- Chunk::verifyMD5 on each fetched chunk,
  * chunk_manager.cc:1548-1556 with verifyChunkChecksum -- and the object is
  * decoded as nxec_decode_object does, in one pass over the chunks (fused
- * kernel for the full stripes when k <= 20, the lost data chunks <= 4 and
- * max_chunk_size is a multiple of 256).  d_ok [ns][n]: byte (s, c) = 1 if
+ * kernel for the full stripes when k <= 20, the lost data chunks <= 4,
+ * max_chunk_size is a multiple of 256 and every chunk read or written ends
+ * within 4 GiB of its stripe, id*M + M <= 2^32 - 1: the layouts
+ * nxec_rs_decode_stripes takes).  d_ok [ns][n]: byte (s, c) = 1 if
  * chunk c of stripe s matched, 0 if not; entries of chunks that were not read
  * are left as they were.  *d_nbad (device, optional, not reset) += mismatches.
  * A stripe with a mismatch decodes to undefined bytes: download d_ok and pass

@@ -98,7 +98,8 @@ __global__ __launch_bounds__(kEmBlock) void k_mul_md5(const MulMd5Args a) {
     // stripe: the lane's part of the address is one 32-bit VGPR, the chunk
     // and step part an SGPR offset -- no 64-bit address pair per source,
     // output and copy (those pushed the copy-through variant into spills).
-    // launch_mul_md5 checks that every offset of a group fits in 32 bits.
+    // launch_mul_md5 keeps every offset of a group within 32 bits: chunk offset
+    // + len by refusing the launch, the lane part by mul_md5_group_cap.
     const __amdgpu_buffer_rsrc_t rsrc_src = em_rsrc(a.src + s0 * a.src_stripe_stride);
     const __amdgpu_buffer_rsrc_t rsrc_dst = em_rsrc(a.dst + s0 * a.dst_stripe_stride);
     const uint32_t vsrc = static_cast<uint32_t>(ls * a.src_stripe_stride) + v * 16;
@@ -418,17 +419,8 @@ const EmKernel kEmProbe[8] = {&k_mul_md5<10, true, 0>, &k_mul_md5<10, true, 1>, 
 
 bool mul_md5_eligible(int k, int rows, int64_t len, const void *src, int64_t src_stripe_stride, const uint32_t *src_off,
                       const void *dst, int64_t dst_stripe_stride, const uint32_t *dst_off, const uint32_t *copy_off) {
-  if (k < 1 || k > kEncMd5MaxK || rows < 0 || rows > kMaxRowsPerPass) return false;
-  if (len <= 0 || len % kEncMd5Step != 0 || len / kEncMd5Step >= (int64_t(1) << 31)) return false;
   if (!tuning().fused_md5) return false;  // probe: two kernels (coding, then MD5)
-  uint64_t bits = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) |
-                  static_cast<uint64_t>(src_stripe_stride) | static_cast<uint64_t>(dst_stripe_stride);
-  for (int j = 0; j < k; j++) bits |= src_off[j];
-  for (int r = 0; r < rows; r++) bits |= dst_off[r];
-  if (copy_off)
-    for (int j = 0; j < k; j++)
-      if (copy_off[j] != kNoCopy) bits |= copy_off[j];
-  return (bits & 15) == 0;
+  return mul_md5_layout_ok(k, rows, len, src, src_stripe_stride, src_off, dst, dst_stripe_stride, dst_off, copy_off);
 }
 
 // The fused kernels ask for up to the whole LDS, and their tables must start
@@ -460,6 +452,16 @@ int launch_mul_md5(const MulMd5Args &in, int num_cus, void *stream) {
   if (per_cu < S) S = per_cu;
   if (tuning().em_stripes > 0)  // probe: stripes per workgroup
     S = std::max<int64_t>(1, std::min<int64_t>(tuning().em_stripes, std::min(kEmMaxStripes, kEmMaxRows / n)));
+  // a lane's offset from its group's first stripe is one 32-bit register: fewer
+  // stripes per group where the stripe stride would carry it past 2^32 - 1
+  int64_t top = 0;
+  for (int j = 0; j < a.k; j++) {
+    top = std::max<int64_t>(top, a.src_off[j]);
+    if (a.any_copy && a.copy_off[j] != kNoCopy) top = std::max<int64_t>(top, a.copy_off[j]);
+  }
+  for (int r = 0; r < a.p; r++) top = std::max<int64_t>(top, a.dst_off[r]);
+  if (top + a.len > kStripeOffMax) return set_error(NXEC_ERR_INVALID, "mul+md5: chunk offset out of range");
+  S = mul_md5_group_cap(S, a.src_stripe_stride, a.dst_stripe_stride, top + a.len);
   a.stripes_per_group = static_cast<int32_t>(S);
   a.hash_prio = tuning().em_prio;
   const int64_t grid = (a.nstripes + S - 1) / S;

@@ -381,8 +381,52 @@ struct MulMd5Args {
   int64_t ok_stripe_stride;
   unsigned long long *nbad;
 };
-// k <= kEncMd5MaxK, 0 <= rows <= 4, len a positive multiple of kEncMd5Step,
-// 16-byte aligned buffers, strides and offsets (NXEC_FUSED_MD5=0 disables, for A/B)
+// The contract of every strided call (include/nxec.h: "chunks of a stripe must
+// lie within 4 GiB"): chunk `idx` of a stripe, `len` bytes at idx * stride,
+// must end at or below byte 2^32 - 1 of the stripe.  *out = its 32-bit offset.
+constexpr int64_t kStripeOffMax = (int64_t(1) << 32) - 1;
+inline bool chunk_off32(int64_t idx, int64_t stride, int64_t len, uint32_t *out) {
+  if (idx < 0 || stride < 0 || len < 0 || (idx > 0 && stride > kStripeOffMax)) return false;
+  const int64_t off = idx * stride;  // idx <= NXEC_MAX_N, stride < 2^32: no overflow
+  if (off + len > kStripeOffMax) return false;
+  *out = static_cast<uint32_t>(off);
+  return true;
+}
+// The layout half of mul_md5_eligible, a pure host function (tests/cpp/
+// md5_layout_test.cc): k <= kEncMd5MaxK, 0 <= rows <= 4, len a positive multiple
+// of kEncMd5Step, 16-byte aligned buffers, strides and offsets, and every
+// source, output and copy offset + len <= 2^32 - 1 -- the rule of the plain
+// calls, so a fused call and its two-kernel fallback accept the same layouts
+// whatever len % 256 is.  (The kernels add the step's byte offset to the
+// chunk's in 32 bits: a chunk that starts below 2^32 and ends above it would
+// wrap into another chunk of the allocation.)
+inline bool mul_md5_layout_ok(int k, int rows, int64_t len, const void *src, int64_t src_stripe_stride,
+                              const uint32_t *src_off, const void *dst, int64_t dst_stripe_stride,
+                              const uint32_t *dst_off, const uint32_t *copy_off = nullptr) {
+  if (k < 1 || k > kEncMd5MaxK || rows < 0 || rows > kMaxRowsPerPass) return false;
+  if (len <= 0 || len % kEncMd5Step != 0 || len / kEncMd5Step >= (int64_t(1) << 31)) return false;
+  if (src_stripe_stride < 0 || dst_stripe_stride < 0) return false;
+  uint64_t bits = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) |
+                  static_cast<uint64_t>(src_stripe_stride) | static_cast<uint64_t>(dst_stripe_stride);
+  int64_t top = 0;  // the largest offset in use
+  for (int j = 0; j < k; j++) bits |= src_off[j], top = std::max<int64_t>(top, src_off[j]);
+  for (int r = 0; r < rows; r++) bits |= dst_off[r], top = std::max<int64_t>(top, dst_off[r]);
+  if (copy_off)
+    for (int j = 0; j < k; j++)
+      if (copy_off[j] != kNoCopy) bits |= copy_off[j], top = std::max<int64_t>(top, copy_off[j]);
+  return (bits & 15) == 0 && top + len <= kStripeOffMax;
+}
+// Stripes per workgroup of k_mul_md5: the largest S' <= S whose group keeps
+// every byte offset from the group's first stripe within 32 bits -- the lane
+// part (S' - 1) * max(src, dst stripe stride) plus `top_end`, the largest chunk
+// offset + len.  At least 1 (one stripe per group has no lane part).
+inline int64_t mul_md5_group_cap(int64_t S, int64_t src_stripe_stride, int64_t dst_stripe_stride, int64_t top_end) {
+  const int64_t ss = std::max(src_stripe_stride, dst_stripe_stride);
+  if (S <= 1 || ss <= 0) return std::max<int64_t>(S, 1);
+  const int64_t room = kStripeOffMax - top_end;
+  return room < 0 ? 1 : std::min(S, room / ss + 1);
+}
+// mul_md5_layout_ok, unless NXEC_FUSED_MD5=0 disables the fused kernels (A/B)
 bool mul_md5_eligible(int k, int rows, int64_t len, const void *src, int64_t src_stripe_stride, const uint32_t *src_off,
                       const void *dst, int64_t dst_stripe_stride, const uint32_t *dst_off,
                       const uint32_t *copy_off = nullptr);

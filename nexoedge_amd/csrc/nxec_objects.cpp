@@ -564,18 +564,17 @@ int nxec_decode_object_verify(nxec_ctx_t *ctx, int n, int k, const int32_t *fail
   };
   if (nf > 0) {
     MulMd5Args a{};
-    bool fused = e <= kMaxRowsPerPass && k <= kEncMd5MaxK && int64_t(n - 1) * M < (int64_t(1) << 32) &&
-                 int64_t(k) * M < (int64_t(1) << 32);
+    bool fused = e <= kMaxRowsPerPass && k <= kEncMd5MaxK;
     if (fused) {
       a.any_copy = 0;
-      for (int j = 0; j < k; j++) {
-        a.src_off[j] = static_cast<uint32_t>(inputs[j] * M);
-        a.copy_off[j] = inputs[j] < k ? static_cast<uint32_t>(inputs[j] * M) : kNoCopy;
+      for (int j = 0; j < k && fused; j++) {
+        fused = chunk_off32(inputs[j], M, M, &a.src_off[j]);  // the copy's offset is the source's: both are id * M
+        a.copy_off[j] = inputs[j] < k ? a.src_off[j] : kNoCopy;
         a.any_copy |= inputs[j] < k;
         a.digest_slot[j] = static_cast<uint8_t>(inputs[j]);
       }
-      for (int r = 0; r < e; r++) a.dst_off[r] = static_cast<uint32_t>(targets[r] * M);
-      fused = mul_md5_eligible(k, e, M, d_chunks, n * M, a.src_off, d_object, k * M, a.dst_off, a.copy_off);
+      for (int r = 0; r < e && fused; r++) fused = chunk_off32(targets[r], M, M, &a.dst_off[r]);
+      fused = fused && mul_md5_eligible(k, e, M, d_chunks, n * M, a.src_off, d_object, k * M, a.dst_off, a.copy_off);
     }
     if (fused) {
       if (e > 0) {

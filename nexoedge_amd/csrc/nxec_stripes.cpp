@@ -54,11 +54,7 @@ int stripes_mul_impl(nxec_ctx_t *ctx, int rows, int k, const unsigned char *coef
   if (gather && any_copy) return set_error(NXEC_ERR_INVALID, "copy_idx is only supported in the strided form");
   // chunk byte offsets inside a stripe (kept 32-bit for the kernels' scalar address math)
   auto chunk_off = [&](int32_t idx, int64_t stride, uint32_t *out) -> bool {
-    if (idx < 0) return false;
-    const int64_t off = static_cast<int64_t>(idx) * stride;
-    if (stride < 0 || off + len > (int64_t(1) << 32) - 1) return false;
-    *out = static_cast<uint32_t>(off);
-    return true;
+    return chunk_off32(idx, stride, len, out);
   };
   for (int j = 0; j < k && !gather; j++) {
     const int32_t si = src_idx ? src_idx[j] : j;
@@ -588,10 +584,11 @@ bool encode_md5_args(int n, int k, const unsigned char *data, int64_t data_cs, i
                      MulMd5Args &a) {
   const int p = n - k;
   if (k > kEncMd5MaxK || p < 1 || p > kMaxRowsPerPass) return false;
-  if (int64_t(k - 1) * data_cs >= (int64_t(1) << 32) || int64_t(p - 1) * par_cs >= (int64_t(1) << 32)) return false;
   a = MulMd5Args{};
-  for (int j = 0; j < k; j++) a.src_off[j] = static_cast<uint32_t>(j * data_cs);
-  for (int r = 0; r < p; r++) a.dst_off[r] = static_cast<uint32_t>(r * par_cs);
+  for (int j = 0; j < k; j++)
+    if (!chunk_off32(j, data_cs, len, &a.src_off[j])) return false;
+  for (int r = 0; r < p; r++)
+    if (!chunk_off32(r, par_cs, len, &a.dst_off[r])) return false;
   if (!mul_md5_eligible(k, p, len, data, data_ss, a.src_off, parity, par_ss, a.dst_off)) return false;
   std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
   nxec_gf_gen_rs_matrix(enc.data(), n, k);  // rs.cc:26
@@ -624,7 +621,10 @@ int nxec_rs_encode_md5_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_s
     return set_error(NXEC_ERR_INVALID, "nxec_rs_encode_md5_stripes: invalid arguments");
   if (nstripes == 0) return NXEC_OK;
   MulMd5Args ea;
-  if (encode_md5_args(n, k, d_stripes, chunk_stride, stripe_stride, d_stripes + int64_t(k) * chunk_stride, chunk_stride,
+  // the parity chunks count from the stripe like the data chunks, as in the two-kernel path below
+  uint32_t last_off = 0;
+  if (chunk_off32(n - 1, chunk_stride, len, &last_off) &&
+      encode_md5_args(n, k, d_stripes, chunk_stride, stripe_stride, d_stripes + int64_t(k) * chunk_stride, chunk_stride,
                       stripe_stride, d_digests, len, nstripes, ea)) {
     int rc = ensure_device(ctx->device);
     if (rc) return rc;
@@ -648,12 +648,12 @@ int nxec_rs_recover_md5_stripes(nxec_ctx_t *ctx, int n, int k, const int32_t *fa
   int ni = 0, mi = 0;
   int rc = nxec_rs_plan(n, k, failed, nfailed, 1, inputs.data(), &ni, &mi, rm.data());  // rs.cc:238-322
   if (rc) return rc;
-  bool fused = k <= kEncMd5MaxK && nfailed <= kMaxRowsPerPass && int64_t(n - 1) * chunk_stride < (int64_t(1) << 32);
+  bool fused = k <= kEncMd5MaxK && nfailed <= kMaxRowsPerPass;
   MulMd5Args a{};
   if (fused) {
-    for (int j = 0; j < k; j++) a.src_off[j] = static_cast<uint32_t>(inputs[j] * chunk_stride);
-    for (int r = 0; r < nfailed; r++) a.dst_off[r] = static_cast<uint32_t>(failed[r] * chunk_stride);
-    fused = mul_md5_eligible(k, nfailed, len, d_stripes, stripe_stride, a.src_off, d_stripes, stripe_stride, a.dst_off);
+    for (int j = 0; j < k && fused; j++) fused = chunk_off32(inputs[j], chunk_stride, len, &a.src_off[j]);
+    for (int r = 0; r < nfailed && fused; r++) fused = chunk_off32(failed[r], chunk_stride, len, &a.dst_off[r]);
+    fused = fused && mul_md5_eligible(k, nfailed, len, d_stripes, stripe_stride, a.src_off, d_stripes, stripe_stride, a.dst_off);
   }
   if (fused) {
     if ((rc = ensure_device(ctx->device))) return rc;

@@ -408,3 +408,46 @@ def test_fused_encode_md5_variants_ab(gpu_ctx, monkeypatch, env, M, nstripes):
             assert np.array_equal(par2[s, i], st[k + i]), (s, i)
         for c in range(n):
             assert dig2[s, c].tobytes().hex() == hashlib.md5(st[c].tobytes()).hexdigest(), (s, c)
+
+
+def test_fused_group_of_two_stripes_more_than_4gib_apart(gpu_ctx, monkeypatch):
+    """NXEC_EM_S=2 asks for two stripes per workgroup.  A lane's offset from its group's first stripe is one
+    32-bit register, so with the stripes 2^32 + 2^20 apart the second stripe's lanes would address 2^20 bytes past
+    the first: the launch caps the group at one stripe there (mul_md5_group_cap), and keeps two where the group's
+    offsets fit.  The buffer spans both stripes, so the wrapped address is inside it.  Reads the probe knobs:
+    built only with `make PROBES=1` (nxec_design_probes()); the product build, which picks one stripe per group
+    for a batch this small anyway, skips."""
+    if not nxec.design_probes():
+        pytest.skip("library built without the design-probe kernels (make PROBES=1)")
+    n, k, M = 6, 4, 16384
+    data = fill_bytes(2 * k * M, 6420).reshape(2, k * M)
+    code = np.stack([oracle.rs_encode(n, k, data[s], M) for s in range(2)])
+    want = np.stack([np.frombuffer(hashlib.md5(code[s, c].tobytes()).digest(), dtype=np.uint8)
+                     for s in range(2) for c in range(n)])
+    monkeypatch.setenv("NXEC_EM_S", "2")
+    nxec.launch_log(True)
+    try:
+        g4 = 1 << 32
+        # (stripe stride, stripes per group).  The data chunks count from the stripe and the parity chunks from the
+        # first of them, so the largest chunk offset + len is k * M: (S - 1) * stride + k * M <= 2^32 - 1 holds two
+        # stripes, one byte more does not
+        for ss, spg in ((g4 + (1 << 20), 1), (g4 - k * M, 1), ((g4 - 1 - k * M) // 16 * 16, 2), (n * M, 2)):
+            buf = nxec.DeviceBuffer(ss + n * M)
+            buf.memset(0xEE)
+            for s in range(2):
+                buf.upload(data[s], s * ss)
+            dig = nxec.DeviceBuffer(2 * n * 16)
+            nxec.launch_log_read()
+            gpu_ctx.rs_encode_md5(n, k, buf.ptr, M, ss, M, 2, dig.ptr)
+            gpu_ctx.sync()
+            recs = nxec.launch_log_read()
+            assert [(r["family"], r["spg"]) for r in recs] == [("k_mul_md5", spg)], (ss, recs)
+            for s in range(2):
+                assert np.array_equal(buf.download(n * M, s * ss), code[s].reshape(-1)), (ss, s)
+            if ss > n * M:  # past stripe 0, and where a wrapped lane offset of stripe 1 would land
+                assert (buf.download(1 << 20, n * M) == 0xEE).all() and (buf.download(1 << 20, 1 << 20) == 0xEE).all(), ss
+            assert np.array_equal(dig.download().reshape(2 * n, 16), want), ss
+            buf.free()
+            dig.free()
+    finally:
+        nxec.launch_log(False)
