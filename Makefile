@@ -109,8 +109,9 @@ build/update_registry_test: tests/cpp/update_registry_test.cc $(LIBDIR)/libnxec.
 update-registry-test: build/update_registry_test
 	build/update_registry_test
 
-# the host rules of the fused multiply + MD5 launches (chunk_off32, mul_md5_layout_ok, mul_md5_group_cap: inline in
-# nxec_internal.h) as a stand-alone host program under ASan + UBSan, no device and no libnxec
+# the inline host rules of nxec_internal.h (chunk_off32 and stripe_fits32, mul_md5_layout_ok, mul_md5_group_cap of the
+# fused multiply + MD5 launches; the row-pass split row_passes / pass_rows / pass_coef) as a stand-alone host program
+# under ASan + UBSan, no device and no libnxec
 build/md5_layout_test: tests/cpp/md5_layout_test.cc $(HDRS)
 	@mkdir -p build
 	g++ -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \

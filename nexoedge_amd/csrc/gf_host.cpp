@@ -157,6 +157,12 @@ int repair_rows(int n, int k, const std::vector<uint8_t> &enc, const int32_t *in
 
 bool valid_nk(int n, int k) { return k > 0 && n >= k && n <= NXEC_MAX_N && k <= NXEC_MAX_K; }
 
+std::vector<uint8_t> rs_parity_rows(int n, int k) {
+  std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
+  nxec_gf_gen_rs_matrix(enc.data(), n, k);
+  return std::vector<uint8_t>(enc.begin() + static_cast<size_t>(k) * k, enc.end());
+}
+
 }  // namespace nxec
 
 extern "C" int nxec_rs_plan(int n, int k, const int32_t *failed, int nfailed, int is_repair, int32_t *input_ids,

@@ -460,7 +460,8 @@ int launch_mul_md5(const MulMd5Args &in, int num_cus, void *stream) {
     if (a.any_copy && a.copy_off[j] != kNoCopy) top = std::max<int64_t>(top, a.copy_off[j]);
   }
   for (int r = 0; r < a.p; r++) top = std::max<int64_t>(top, a.dst_off[r]);
-  if (top + a.len > kStripeOffMax) return set_error(NXEC_ERR_INVALID, "mul+md5: chunk offset out of range");
+  // the rule for the chunk that starts furthest into the stripe: chunk 1 of a stride of `top`
+  if (!stripe_fits32(2, top, a.len)) return set_error(NXEC_ERR_INVALID, "mul+md5: chunk offset out of range");
   S = mul_md5_group_cap(S, a.src_stripe_stride, a.dst_stripe_stride, top + a.len);
   a.stripes_per_group = static_cast<int32_t>(S);
   a.hash_prio = tuning().em_prio;

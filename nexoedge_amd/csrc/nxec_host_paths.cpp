@@ -38,10 +38,9 @@ int nxec_rs_encode_host_batch(nxec_ctx_t *ctx, int n, int k, const unsigned char
         static_cast<const unsigned char *>(host_device_view_range(h_data, static_cast<size_t>(nstripes * k * len)));
     unsigned char *dp = static_cast<unsigned char *>(host_device_view_range(h_parity, static_cast<size_t>(nstripes * p * len)));
     if (dd && dp) {
-      std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
-      nxec_gf_gen_rs_matrix(enc.data(), n, k);
+      const std::vector<uint8_t> prows = rs_parity_rows(n, k);
       hipStream_t st = pick_stream(ctx, nullptr);
-      rc = nxec_stripes_mul(ctx, p, k, enc.data() + static_cast<size_t>(k) * k, dd, nullptr, len, k * len, dp, nullptr,
+      rc = nxec_stripes_mul(ctx, p, k, prows.data(), dd, nullptr, len, k * len, dp, nullptr,
                             len, p * len, nullptr, len, nstripes, st);
       if (rc) return rc;
       return hip_check(hipStreamSynchronize(st), "encode_host_batch (direct) sync");
@@ -51,8 +50,7 @@ int nxec_rs_encode_host_batch(nxec_ctx_t *ctx, int n, int k, const unsigned char
   batch_stripes = std::min(batch_stripes, nstripes);
   const int64_t nbatches = (nstripes + batch_stripes - 1) / batch_stripes;
   batch_stripes = (nstripes + nbatches - 1) / nbatches;  // equal batches
-  std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
-  nxec_gf_gen_rs_matrix(enc.data(), n, k);
+  const std::vector<uint8_t> prows = rs_parity_rows(n, k);
   const size_t dbytes = static_cast<size_t>(batch_stripes) * k * len, pbytes = static_cast<size_t>(batch_stripes) * p * len;
   std::unique_lock<std::mutex> lk;
   ObjStage priv, *pstg = nullptr;
@@ -73,7 +71,7 @@ int nxec_rs_encode_host_batch(nxec_ctx_t *ctx, int n, int k, const unsigned char
     if (!rc) rc = hip_check(hipEventRecord(stg.h2d_done[slot], st), "H2D event");
     prev = slot;
     if (!rc)
-      rc = nxec_stripes_mul(ctx, p, k, enc.data() + static_cast<size_t>(k) * k, dbuf, nullptr, len, k * len, pbuf,
+      rc = nxec_stripes_mul(ctx, p, k, prows.data(), dbuf, nullptr, len, k * len, pbuf,
                             nullptr, len, p * len, nullptr, len, ns, st);
     if (!rc)
       rc = hip_check(hipMemcpyAsync(h_parity + s0 * p * len, pbuf, static_cast<size_t>(ns) * p * len,
@@ -548,9 +546,8 @@ int nxec_encode_object_host(nxec_ctx_t *ctx, int n, int k, const unsigned char *
   // count), so batches are large and the slots' streams run concurrently
   if (batch_stripes <= 0) batch_stripes = std::max<int64_t>(1, (int64_t(1) << 30) / (M * n));
   batch_stripes = std::min(batch_stripes, nst);
-  std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
-  nxec_gf_gen_rs_matrix(enc.data(), n, k);
-  const uint8_t *prow = enc.data() + static_cast<size_t>(k) * k;
+  const std::vector<uint8_t> prows = rs_parity_rows(n, k);
+  const uint8_t *prow = prows.data();
   // equal batches: a short last batch would add one whole MD5 chain time
   // (~10 ms for 1 MiB chunks) after everything else has drained
   const int64_t nbatches = (nst + batch_stripes - 1) / batch_stripes;

@@ -38,6 +38,7 @@
 
 #include "nxec_device.h"
 #include "nxec_internal.h"
+#include "nxec_runtime.h"
 #include "nxec_scrub_rule.h"
 
 namespace nxec {
@@ -1234,10 +1235,6 @@ static_assert(default_r(kUpdateMaxK16) == 16 && default_r(kUpdateMaxK16 + 1) == 
 static_assert(update_lds(kMaxRaggedK) <= kLdsBytes, "the widest update tables and the ring fit");
 UpdateFn update_fn(int k) { return k <= kUpdateMaxK16 ? &k_update_vec<16> : &k_update_vec<8>; }
 
-int hip_fail(hipError_t e, const char *what) {
-  return set_error(NXEC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-
 // LDS replication policy (the LDS-replication probe overrides it, nxec_tuning.h).
 int choose_r(int k, bool tunable) {
   if (k > kMaxTemplK) return 1;
@@ -1429,7 +1426,7 @@ int reset_queue_slots(int first, int count, hipStream_t st) {
     e = hipMemsetAsync(static_cast<uint8_t *>(base) + static_cast<size_t>(first) * 128, 0,
                        static_cast<size_t>(count) * 128, st);
   }
-  return e == hipSuccess ? NXEC_OK : hip_fail(e, "tile-queue reset");
+  return hip_check(e, "tile-queue reset");
 }
 
 int launch_failed(hipError_t e, const char *family, int slot, hipStream_t st) {
@@ -1438,19 +1435,39 @@ int launch_failed(hipError_t e, const char *family, int slot, hipStream_t st) {
   return rc;
 }
 
+// The launch of every kernel outside the tile queue, 256 threads a workgroup;
+// `name` is the kernel's in the error text.  A launch record, where the kernel
+// has one, is its caller's.
+template <class... Params, class... Args>
+int plain_launch(const char *name, void (*fn)(Params...), int64_t grid, size_t lds, void *stream, const Args &...args) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(256), lds, st, args...);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? NXEC_OK : launch_failed(e, name, -1, st);
+}
+
+// Grid of the byte kernels over `total` bytes or 16-byte units: 256 a workgroup, at most 8 workgroups per CU.
+int64_t byte_grid(int64_t total, int num_cus) {
+  return std::min<int64_t>((total + 255) / 256, static_cast<int64_t>(num_cus) * 8);
+}
+
 // What one launch of a tile-queue kernel (k_mul_vec, k_mul_perm, k_scrub_vec,
 // k_mul_ragged; k_mul_vec_dyn shares k_mul_vec's path) used.  The launch and
 // its record line both read this, so the record cannot drift from the launch.
+// The constructor takes what every family has; a family sets its other fields by name.
 struct QueueLaunch {
   const char *family, *kkey;  // kkey: "k", or "kd" for the scrub
-  int k, rows, r;
-  int gather, copy, full;  // -1: the family has no such form (the key is left out)
-  int pf, q;
-  uint32_t tpg, sg;  // sg 0: no stripe groups (left out)
+  int k, rows, r, pf;
+  uint32_t tpg;
   int64_t grid;
   int lds;
-  int32_t slot;
+  int gather = -1, copy = -1, full = -1;  // -1: the family has no such form (the key is left out)
+  int q = 1;
+  uint32_t sg = 0;             // 0: no stripe groups (left out)
+  int32_t slot = 0;            // drawn by queue_launch
   const char *tail = nullptr;  // family-specific keys after the slot
+  QueueLaunch(const char *family, const char *kkey, int k, int rows, int r, int pf, uint32_t tpg, int64_t grid, int lds)
+      : family(family), kkey(kkey), k(k), rows(rows), r(r), pf(pf), tpg(tpg), grid(grid), lds(lds) {}
 };
 
 void record_launch(const QueueLaunch &l) {
@@ -1512,29 +1529,27 @@ int launch_mul(const MulArgs &a, bool vec_ok, int num_cus, void *stream) {
       b.vec_begin = a.vec_begin + begin;
       b.vec_count = count;
       const LaunchInfo li = plan_launch(b.k, b.rows, count, b.nstripes, num_cus, full, copy, gather);
-      QueueLaunch l{li.perm ? "k_mul_perm" : dyn ? "k_mul_vec_dyn" : "k_mul_vec", "k", b.k, b.rows,
-                    li.lds_copies, gather, copy, full,
-                    li.perm ? perm_prefetch(b.k) : !dyn && vec_prefetch(b.k, copy, full),
-                    li.perm || (!dyn && vec_queued(b.k, li.lds_copies)), dyn ? 0 : tpg, dyn ? 1 : sg, li.grid,
-                    li.lds_bytes, 0};
+      QueueLaunch l(li.perm ? "k_mul_perm" : dyn ? "k_mul_vec_dyn" : "k_mul_vec", "k", b.k, b.rows, li.lds_copies,
+                    li.perm ? perm_prefetch(b.k) : !dyn && vec_prefetch(b.k, copy, full), dyn ? 0 : tpg, li.grid,
+                    li.lds_bytes);
+      l.gather = gather;
+      l.copy = copy;
+      l.full = full;
+      l.q = li.perm || (!dyn && vec_queued(b.k, li.lds_copies));
+      l.sg = dyn ? 1 : sg;
       return queue_launch(mul_kernel(li, b.k, gather, copy, full), b, b.queue_slot, l, st,
                           !dyn && !tuning().static_order);
     });
     if (rc) return rc;
   }
   if (a.byte_begin < a.len) {
-    const int64_t total = (a.len - a.byte_begin) * a.nstripes;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > static_cast<int64_t>(num_cus) * 8) blocks = static_cast<int64_t>(num_cus) * 8;
-    KernelFn fn = a.src_ptrs ? &k_mul_bytes<true> : &k_mul_bytes<false>;
+    const int64_t blocks = byte_grid((a.len - a.byte_begin) * a.nstripes, num_cus);
     if (launch_log_on())
       launch_log_append("family=k_mul_bytes k=%d rows=%d r=1 gather=%d copy=%d full=0 pf=0 q=0 tpg=0 sg=1 grid=%lld "
                         "byte_begin=%lld",
                         a.k, a.rows, a.src_ptrs != nullptr, a.any_copy != 0, static_cast<long long>(blocks),
                         static_cast<long long>(a.byte_begin));
-    hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(blocks)), dim3(256), bytes_lds(a.k), st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch k_mul_bytes");
+    return plain_launch("k_mul_bytes", a.src_ptrs ? &k_mul_bytes<true> : &k_mul_bytes<false>, blocks, bytes_lds(a.k), st, a);
   }
   return NXEC_OK;
 }
@@ -1565,23 +1580,22 @@ int launch_scrub_detect(const ScrubArgs &a0, bool vec_ok, int num_cus, void *str
       b.m.vec_begin = begin;
       b.m.vec_count = count;
       const int64_t ntiles = (count + kBlock - 1) / kBlock * m.nstripes;
-      QueueLaunch l{"k_scrub_vec", "kd", m.k, m.rows, default_r(m.k), -1, -1, full,
-                    scrub_prefetch(m.k + m.rows, full), 1, m.tiles_per_grab, m.stripe_group,
-                    std::min<int64_t>(num_cus, ntiles), 0, 0};
-      return queue_launch(scrub_kernel(m.k, m.rows, full, &l.lds), b, b.m.queue_slot, l, st);
+      int lds = 0;
+      const auto fn = scrub_kernel(m.k, m.rows, full, &lds);
+      QueueLaunch l("k_scrub_vec", "kd", m.k, m.rows, default_r(m.k), scrub_prefetch(m.k + m.rows, full),
+                    m.tiles_per_grab, std::min<int64_t>(num_cus, ntiles), lds);
+      l.full = full;
+      l.sg = m.stripe_group;
+      return queue_launch(fn, b, b.m.queue_slot, l, st);
     });
     if (rc) return rc;
   }
   if (m.byte_begin < m.len) {
-    const int64_t total = (m.len - m.byte_begin) * m.nstripes;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > static_cast<int64_t>(num_cus) * 8) blocks = static_cast<int64_t>(num_cus) * 8;
+    const int64_t blocks = byte_grid((m.len - m.byte_begin) * m.nstripes, num_cus);
     if (launch_log_on())
       launch_log_append("family=k_scrub_bytes kd=%d rows=%d grid=%lld byte_begin=%lld", m.k, m.rows,
                         static_cast<long long>(blocks), static_cast<long long>(m.byte_begin));
-    hipLaunchKernelGGL(k_scrub_bytes, dim3(static_cast<unsigned>(blocks)), dim3(256), bytes_lds(m.k), st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch k_scrub_bytes");
+    return plain_launch("k_scrub_bytes", k_scrub_bytes, blocks, bytes_lds(m.k), st, a);
   }
   return NXEC_OK;
 }
@@ -1591,17 +1605,12 @@ int launch_scrub_locate(const ScrubLocateArgs &a, void *stream) {
   if (a.nstripes >= (int64_t(1) << 31)) return set_error(NXEC_ERR_INVALID, "scrub: too many stripes for one launch");
   const int m = a.n - a.k;
   const size_t lds = static_cast<size_t>((m * a.k + 15) / 16 * 16) + static_cast<size_t>(m) * 256;
-  hipLaunchKernelGGL(k_scrub_locate, dim3(static_cast<unsigned>(a.nstripes)), dim3(256), lds,
-                     static_cast<hipStream_t>(stream), a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NXEC_OK : hip_fail(e, "launch k_scrub_locate");
+  return plain_launch("k_scrub_locate", k_scrub_locate, a.nstripes, lds, stream, a);
 }
 
 int reset_work_queues(void *stream) {
   const int rc = reset_queue_slots(0, 0, static_cast<hipStream_t>(stream));
-  if (rc) return rc;
-  const hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? NXEC_OK : hip_fail(e, "tile-queue reset sync");
+  return rc ? rc : hip_check(hipStreamSynchronize(static_cast<hipStream_t>(stream)), "tile-queue reset sync");
 }
 
 int debug_poison_next_queue_slot(uint32_t next_tile) {
@@ -1611,16 +1620,15 @@ int debug_poison_next_queue_slot(uint32_t next_tile) {
   if (e == hipSuccess)
     e = hipMemcpy(static_cast<uint8_t *>(base) + static_cast<size_t>(slot) * 128, &next_tile, sizeof(next_tile),
                   hipMemcpyHostToDevice);
-  return e == hipSuccess ? NXEC_OK : hip_fail(e, "tile-queue poison");
+  return hip_check(e, "tile-queue poison");
 }
 
 int launch_mul_list(int rows, int k, const uint8_t *coeffs, const ListStripe *d_stripes, const int64_t *d_prefix,
                     int64_t nstripes, int64_t total_units, int num_cus, void *stream) {
   if (nstripes <= 0 || total_units <= 0 || rows <= 0) return NXEC_OK;
   if (k < 1 || k > NXEC_MAX_K) return set_error(NXEC_ERR_INVALID, "k=%d out of range", k);
-  int64_t blocks = (total_units + 255) / 256;
-  if (blocks > static_cast<int64_t>(num_cus) * 8) blocks = static_cast<int64_t>(num_cus) * 8;
-  for (int r0 = 0; r0 < rows; r0 += kMaxRowsPerPass) {
+  const int64_t blocks = byte_grid(total_units, num_cus);
+  for (int p = 0; p < row_passes(rows); p++) {
     ListArgs a;
     std::memset(&a, 0, sizeof(a));
     a.stripes = d_stripes;
@@ -1628,16 +1636,11 @@ int launch_mul_list(int rows, int k, const uint8_t *coeffs, const ListStripe *d_
     a.nstripes = nstripes;
     a.total = total_units;
     a.k = k;
-    a.rows = rows - r0 < kMaxRowsPerPass ? rows - r0 : kMaxRowsPerPass;
-    a.row0 = r0;
-    for (int r = 0; r < a.rows; r++)
-      for (int j = 0; j < k; j++) a.coef[r * k + j] = coeffs[static_cast<size_t>(r0 + r) * k + j];
+    a.rows = pass_coef(rows, k, coeffs, p, a.coef);
+    a.row0 = p * kMaxRowsPerPass;
     if (launch_log_on())
       launch_log_append("family=k_mul_list k=%d rows=%d grid=%lld", k, a.rows, static_cast<long long>(blocks));
-    hipLaunchKernelGGL(k_mul_list, dim3(static_cast<unsigned>(blocks)), dim3(256), bytes_lds(k),
-                       static_cast<hipStream_t>(stream), a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch k_mul_list");
+    if (int rc = plain_launch("k_mul_list", k_mul_list, blocks, bytes_lds(k), stream, a)) return rc;
   }
   return NXEC_OK;
 }
@@ -1648,7 +1651,7 @@ int launch_mul_ragged(int rows, int k, const uint8_t *coeffs, const ListStripe *
   if (k < 1 || k > kMaxRaggedK) return set_error(NXEC_ERR_INVALID, "ragged launch: k=%d unsupported", k);
   if (ntiles >= (int64_t(1) << 32)) return set_error(NXEC_ERR_INVALID, "ragged launch: too many tiles");
   const int64_t grid = std::min<int64_t>(num_cus, ntiles);
-  for (int r0 = 0; r0 < rows; r0 += kMaxRowsPerPass) {
+  for (int p = 0; p < row_passes(rows); p++) {
     RaggedArgs a;
     std::memset(&a, 0, sizeof(a));
     a.stripes = d_stripes;
@@ -1656,13 +1659,10 @@ int launch_mul_ragged(int rows, int k, const uint8_t *coeffs, const ListStripe *
     a.stripe_tile0 = d_stripe_tile0;
     a.ntiles = static_cast<uint32_t>(ntiles);
     a.k = k;
-    a.rows = rows - r0 < kMaxRowsPerPass ? rows - r0 : kMaxRowsPerPass;
-    a.row0 = r0;
+    a.rows = pass_coef(rows, k, coeffs, p, a.coef);
+    a.row0 = p * kMaxRowsPerPass;
     a.tiles_per_grab = tiles_per_grab(k, a.rows, 0);
-    for (int r = 0; r < a.rows; r++)
-      for (int j = 0; j < k; j++) a.coef[r * k + j] = coeffs[static_cast<size_t>(r0 + r) * k + j];
-    QueueLaunch l{"k_mul_ragged", "k", k, a.rows, default_r(k), -1, -1, -1, ragged_prefetch(k), 1,
-                  a.tiles_per_grab, 0, grid, ragged_lds(k), 0};
+    QueueLaunch l("k_mul_ragged", "k", k, a.rows, default_r(k), ragged_prefetch(k), a.tiles_per_grab, grid, ragged_lds(k));
     if (int rc = queue_launch(kRagged[k - 1], a, a.queue_slot, l, static_cast<hipStream_t>(stream))) return rc;
   }
   return NXEC_OK;
@@ -1693,8 +1693,9 @@ int launch_mixed(int k, bool full, const uint8_t *src, int64_t stripe_stride, ui
   char tail[64];
   std::snprintf(tail, sizeof tail, "segs=%lld stripes=%lld", static_cast<long long>(nsegs),
                 static_cast<long long>(nstripes));
-  QueueLaunch l{kMixedFamily[full], "k", k, kMaxRowsPerPass, default_r(k), -1, -1, -1, ragged_prefetch(k), 1,
-                a.tiles_per_grab, 0, std::min<int64_t>(num_cus, a.ntiles), mixed_lds(k), 0, tail};
+  QueueLaunch l(kMixedFamily[full], "k", k, kMaxRowsPerPass, default_r(k), ragged_prefetch(k), a.tiles_per_grab,
+                std::min<int64_t>(num_cus, a.ntiles), mixed_lds(k));
+  l.tail = tail;
   if (full) return queue_launch(kDecodeMixed[k - 1], a, a.queue_slot, l, static_cast<hipStream_t>(stream));
   return queue_launch<MixedArgs>(kMixed[k - 1], a, a.queue_slot, l, static_cast<hipStream_t>(stream));
 }
@@ -1707,10 +1708,8 @@ void update_pass(UpdateArgs &a, int k, int rows, int row0, const uint8_t *coef, 
   a.rows = rows;
   a.last = last;
   a.chunk_stride = static_cast<uint32_t>(chunk_stride);
-  for (int r = 0; r < rows; r++) {
-    a.par_off[r] = static_cast<uint32_t>((k + row0 + r) * chunk_stride);
-    for (int j = 0; j < k; j++) a.coef[r * k + j] = coef[static_cast<size_t>(r) * k + j];
-  }
+  pass_coef(rows, k, coef, 0, a.coef);  // the caller's rows are this pass's: coef starts at row0
+  for (int r = 0; r < rows; r++) a.par_off[r] = static_cast<uint32_t>((k + row0 + r) * chunk_stride);
 }
 }  // namespace
 
@@ -1731,8 +1730,9 @@ int launch_update_vec(int k, int rows, int row0, const uint8_t *coef, uint8_t *b
   char tail[96];
   std::snprintf(tail, sizeof tail, "tiles=%lld updates=%lld round=%d pass=%d last=%d", static_cast<long long>(ntiles),
                 static_cast<long long>(nupdates), round, pass, last ? 1 : 0);
-  QueueLaunch l{"k_update_vec", "k", k, rows, default_r(k), -1, -1, -1, 1, 1, a.tiles_per_grab, 0,
-                std::min<int64_t>(num_cus, ntiles), update_lds(k), 0, tail};
+  QueueLaunch l("k_update_vec", "k", k, rows, default_r(k), 1, a.tiles_per_grab, std::min<int64_t>(num_cus, ntiles),
+                update_lds(k));
+  l.tail = tail;
   return queue_launch(update_fn(k), a, a.queue_slot, l, static_cast<hipStream_t>(stream));
 }
 
@@ -1749,24 +1749,18 @@ int launch_update_bytes(int k, int rows, int row0, const uint8_t *coef, uint8_t 
   a.nitems = nitems;
   a.nbytes = nbytes;
   a.queue_slot = -1;
-  const int64_t blocks = std::min<int64_t>((nbytes + 255) / 256, static_cast<int64_t>(num_cus) * 8);
+  const int64_t blocks = byte_grid(nbytes, num_cus);
   if (launch_log_on())
     launch_log_append("family=k_update_bytes k=%d rows=%d r=1 grid=%lld items=%lld round=%d pass=%d last=%d", k, rows,
                       static_cast<long long>(blocks), static_cast<long long>(nitems), round, pass, last ? 1 : 0);
-  hipLaunchKernelGGL(k_update_bytes, dim3(static_cast<unsigned>(blocks)), dim3(256), bytes_lds(k),
-                     static_cast<hipStream_t>(stream), a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NXEC_OK : hip_fail(e, "launch k_update_bytes");
+  return plain_launch("k_update_bytes", k_update_bytes, blocks, bytes_lds(k), stream, a);
 }
 
 int launch_pad_chunks(const PadChunks *d_items, const uint32_t *d_bstart, int64_t nitems, int64_t nblocks,
                       void *stream) {
   if (nitems <= 0 || nblocks <= 0) return NXEC_OK;
   if (nblocks >= (int64_t(1) << 31)) return set_error(NXEC_ERR_INVALID, "pad-chunks launch too large");
-  hipLaunchKernelGGL(k_pad_chunks, dim3(static_cast<unsigned>(nblocks)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     d_items, d_bstart, nitems);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NXEC_OK : hip_fail(e, "launch k_pad_chunks");
+  return plain_launch("k_pad_chunks", k_pad_chunks, nblocks, 0, stream, d_items, d_bstart, nitems);
 }
 
 int launch_copy16(void *dst, const void *src, size_t bytes, int num_cus, void *stream) {
@@ -1775,26 +1769,18 @@ int launch_copy16(void *dst, const void *src, size_t bytes, int num_cus, void *s
     return set_error(NXEC_ERR_INVALID, "copy16: unaligned");
   const int64_t n = static_cast<int64_t>(bytes / 16);
   const int64_t blocks = std::min<int64_t>((n + 255) / 256, static_cast<int64_t>(num_cus) * 4);
-  hipLaunchKernelGGL(k_copy16, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<u32x4 *>(dst), static_cast<const u32x4 *>(src), n);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NXEC_OK : hip_fail(e, "launch k_copy16");
+  return plain_launch("k_copy16", k_copy16, blocks, 0, stream, static_cast<u32x4 *>(dst),
+                      static_cast<const u32x4 *>(src), n);
 }
 
 int launch_fill(void *d, size_t bytes, uint64_t seed, void *stream) {
   if (bytes == 0) return NXEC_OK;
-  hipLaunchKernelGGL(k_fill, dim3(2048), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<uint8_t *>(d),
-                     static_cast<int64_t>(bytes), seed);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NXEC_OK : hip_fail(e, "launch k_fill");
+  return plain_launch("k_fill", k_fill, 2048, 0, stream, static_cast<uint8_t *>(d), static_cast<int64_t>(bytes), seed);
 }
 
 int launch_checksum(const void *d, size_t bytes, uint64_t *d_out, void *stream) {
-  hipLaunchKernelGGL(k_checksum, dim3(1024), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const uint8_t *>(d), static_cast<int64_t>(bytes),
-                     reinterpret_cast<unsigned long long *>(d_out));
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NXEC_OK : hip_fail(e, "launch k_checksum");
+  return plain_launch("k_checksum", k_checksum, 1024, 0, stream, static_cast<const uint8_t *>(d),
+                      static_cast<int64_t>(bytes), reinterpret_cast<unsigned long long *>(d_out));
 }
 
 }  // namespace nxec

@@ -81,8 +81,7 @@ void mixed_plan(MixedMode mode, int n, int k, const uint8_t *alive, int64_t nstr
           }
           if (rc == NXEC_OK) {
             verdict = static_cast<int32_t>(p.plans.size());
-            const int64_t t = static_cast<int64_t>(pl.targets.size());
-            p.nsegments += t ? (t + kMaxRowsPerPass - 1) / kMaxRowsPerPass : 1;  // t == 0: Decode's copy-only plan
+            p.nsegments += row_passes(static_cast<int>(pl.targets.size()));  // no target: Decode's copy-only plan
             p.plans.push_back(std::move(pl));
           } else {
             verdict = NXEC_RECOVER_SINGULAR;
@@ -117,20 +116,18 @@ void mixed_tables(const MixedPlan &plan, int k, int64_t chunk_stride, int64_t ou
     const MixedPlan::Plan &pl = plan.plans[pi];
     seg0[pi] = static_cast<uint32_t>(segs.size());
     const int nt = static_cast<int>(pl.targets.size());
-    for (int r0 = 0; r0 == 0 || r0 < nt; r0 += kMaxRowsPerPass) {
+    for (int p = 0; p < row_passes(nt); p++) {
+      const int r0 = p * kMaxRowsPerPass;
       MixedSeg g;
       std::memset(&g, 0, sizeof(g));
-      g.rows = static_cast<uint32_t>(nt - r0 < kMaxRowsPerPass ? nt - r0 : kMaxRowsPerPass);
+      g.rows = static_cast<uint32_t>(pass_coef(nt, k, pl.rows.data(), p, g.coef));
       for (int j = 0; j < kMaxRaggedK; j++) g.copy_off[j] = kNoCopy;
       for (int j = 0; j < k; j++) {
         g.src_off[j] = static_cast<uint32_t>(pl.inputs[j] * chunk_stride);
         // surviving data chunks are unit rows of the inverse: copies of their input, made once
         if (copy && r0 == 0 && pl.inputs[j] < k) g.copy_off[j] = static_cast<uint32_t>(pl.inputs[j] * out_chunk_stride);
       }
-      for (uint32_t r = 0; r < g.rows; r++) {
-        g.dst_off[r] = static_cast<uint32_t>(pl.targets[r0 + r] * out_chunk_stride);
-        std::memcpy(g.coef + r * k, pl.rows.data() + static_cast<size_t>(r0 + r) * k, k);
-      }
+      for (uint32_t r = 0; r < g.rows; r++) g.dst_off[r] = static_cast<uint32_t>(pl.targets[r0 + r] * out_chunk_stride);
       segs.push_back(g);
     }
   }

@@ -43,9 +43,8 @@ int nxec_encode_object(nxec_ctx_t *ctx, int n, int k, const unsigned char *d_obj
   rc = ensure_device(ctx->device);
   if (rc) return rc;
   hipStream_t st = pick_stream(ctx, stream);
-  std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
-  nxec_gf_gen_rs_matrix(enc.data(), n, k);
-  const uint8_t *prow = enc.data() + static_cast<size_t>(k) * k;
+  const std::vector<uint8_t> prows = rs_parity_rows(n, k);
+  const uint8_t *prow = prows.data();
   // full stripes: data chunks are read in place from the object (no copy of
   // rs.cc:80), parity chunk (s, i) at d_parity + (s*p + i)*M; with digests
   // wanted, the encode and the MD5 of all n chunks run as one kernel
@@ -129,9 +128,8 @@ int nxec_encode_objects_ex(nxec_ctx_t *ctx, int n, int k, int nobjects, const un
   rc = ensure_device(ctx->device);
   if (rc) return rc;
   hipStream_t st = pick_stream(ctx, stream);
-  std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
-  nxec_gf_gen_rs_matrix(enc.data(), n, k);
-  const uint8_t *prow = enc.data() + static_cast<size_t>(k) * k;
+  const std::vector<uint8_t> prows = rs_parity_rows(n, k);
+  const uint8_t *prow = prows.data();
 
   // Host plan, every table to the device in one copy:
   //  * full stripes of every object: gather pointer tables, one k_mul_vec launch

@@ -14,10 +14,8 @@ extern "C" int nxec_rs_syndrome_locate(int n, int k, const unsigned char *syndro
   if (!valid_nk(n, k)) return set_error(NXEC_ERR_INVALID, "invalid (n,k)=(%d,%d)", n, k);
   if (!chunk || (n > k && !syndrome)) return set_error(NXEC_ERR_INVALID, "nxec_rs_syndrome_locate: null argument");
   static_assert(scrub::kClean == NXEC_SCRUB_CLEAN && scrub::kUnlocated == NXEC_SCRUB_UNLOCATED, "status codes");
-  std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
-  nxec_gf_gen_rs_matrix(enc.data(), n, k);
   uint8_t e = 0;
-  *chunk = scrub::locate(n, k, enc.data() + static_cast<size_t>(k) * k, [&](int r) { return syndrome[r]; }, &e);
+  *chunk = scrub::locate(n, k, rs_parity_rows(n, k).data(), [&](int r) { return syndrome[r]; }, &e);
   if (error) *error = e;
   return NXEC_OK;
 }

@@ -53,16 +53,13 @@ int stripes_mul_impl(nxec_ctx_t *ctx, int rows, int k, const unsigned char *coef
   a.dst_ptr_rows = rows;
   if (gather && any_copy) return set_error(NXEC_ERR_INVALID, "copy_idx is only supported in the strided form");
   // chunk byte offsets inside a stripe (kept 32-bit for the kernels' scalar address math)
-  auto chunk_off = [&](int32_t idx, int64_t stride, uint32_t *out) -> bool {
-    return chunk_off32(idx, stride, len, out);
-  };
   for (int j = 0; j < k && !gather; j++) {
     const int32_t si = src_idx ? src_idx[j] : j;
-    if (!chunk_off(si, src_cs, &a.src_off[j]))
+    if (!chunk_off32(si, src_cs, len, &a.src_off[j]))
       return set_error(NXEC_ERR_INVALID, "src_idx[%d]=%d: offset out of range (chunks of a stripe must lie within 4 GiB)",
                        j, si);
     a.copy_off[j] = kNoCopy;
-    if (copy_idx && copy_idx[j] >= 0 && !chunk_off(copy_idx[j], dst_cs, &a.copy_off[j]))
+    if (copy_idx && copy_idx[j] >= 0 && !chunk_off32(copy_idx[j], dst_cs, len, &a.copy_off[j]))
       return set_error(NXEC_ERR_INVALID, "copy_idx[%d]=%d: offset out of range", j, copy_idx[j]);
   }
 
@@ -78,22 +75,19 @@ int stripes_mul_impl(nxec_ctx_t *ctx, int rows, int k, const unsigned char *coef
 
   const int64_t max_stripes = max_stripes_per_launch(vec_count);
 
-  const int passes = rows == 0 ? 1 : (rows + kMaxRowsPerPass - 1) / kMaxRowsPerPass;
-  for (int p = 0; p < passes; p++) {
+  for (int p = 0; p < row_passes(rows); p++) {
     const int r0 = p * kMaxRowsPerPass;
-    const int pr = std::min(kMaxRowsPerPass, rows - r0);
-    a.rows = std::max(pr, 0);
+    a.rows = pass_coef(rows, k, coeffs, p, a.coef);
     a.any_copy = (p == 0 && any_copy) ? 1 : 0;
     a.dst_ptr_row0 = r0;
     for (int r = 0; r < kMaxRowsPerPass; r++) {
       const int rr = r0 + r;
       a.dst_off[r] = 0;
-      if (r < pr && !gather) {
+      if (r < a.rows && !gather) {
         const int32_t di = dst_idx ? dst_idx[rr] : rr;
-        if (!chunk_off(di, dst_cs, &a.dst_off[r]))
+        if (!chunk_off32(di, dst_cs, len, &a.dst_off[r]))
           return set_error(NXEC_ERR_INVALID, "dst_idx[%d]=%d: offset out of range", rr, di);
       }
-      for (int j = 0; j < k; j++) a.coef[r * k + j] = r < pr ? coeffs[static_cast<size_t>(rr) * k + j] : 0;
     }
     for (int64_t s0 = 0; s0 < nstripes; s0 += max_stripes) {
       MulArgs b = a;
@@ -252,7 +246,7 @@ static int mixed_stripes(nxec_ctx_t *ctx, MixedMode mode, int n, int k, const un
   const bool work = plan.nstripes_planned > 0 && len > 0;
   if (work && (!src || !dst)) return set_error(NXEC_ERR_INVALID, "null stripe buffer");
   // chunk byte offsets inside a stripe stay 32-bit (the kernels' scalar address math); the decode checked before planning
-  if (recover && work && (cs < 0 || static_cast<int64_t>(n - 1) * cs + len > (int64_t(1) << 32) - 1))
+  if (recover && work && !stripe_fits32(n, cs, len))
     return set_error(NXEC_ERR_INVALID, "mixed recover: chunk offset out of range (chunks of a stripe must lie within 4 GiB)");
   int rc = NXEC_OK;
   if (work) {
@@ -314,13 +308,10 @@ int nxec_rs_encode_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_strip
                            int64_t stripe_stride, int64_t len, int64_t nstripes, void *stream) {
   if (!valid_nk(n, k)) return set_error(NXEC_ERR_INVALID, "invalid (n,k)=(%d,%d)", n, k);
   if (n == k) return NXEC_OK;
-  std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
-  nxec_gf_gen_rs_matrix(enc.data(), n, k);  // rs.cc:26
   std::vector<int32_t> dst(n - k);
   for (int i = k; i < n; i++) dst[i - k] = i;
-  return nxec_stripes_mul(ctx, n - k, k, enc.data() + static_cast<size_t>(k) * k, d_stripes, nullptr, chunk_stride,
-                          stripe_stride, d_stripes, dst.data(), chunk_stride, stripe_stride, nullptr, len, nstripes,
-                          stream);
+  return nxec_stripes_mul(ctx, n - k, k, rs_parity_rows(n, k).data(), d_stripes, nullptr, chunk_stride, stripe_stride,
+                          d_stripes, dst.data(), chunk_stride, stripe_stride, nullptr, len, nstripes, stream);
 }
 
 int nxec_rs_recover_stripes(nxec_ctx_t *ctx, int n, int k, const int32_t *failed, int nfailed,
@@ -363,9 +354,7 @@ int nxec_rs_update_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_strip
   if (!d_stripes) return set_error(NXEC_ERR_INVALID, "null stripe buffer");
   if ((rc = ensure_device(ctx->device))) return rc;
   hipStream_t st = pick_stream(ctx, stream);
-  std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
-  nxec_gf_gen_rs_matrix(enc.data(), n, k);
-  const uint8_t *parity = enc.data() + static_cast<size_t>(k) * k;  // (n-k) x k
+  const std::vector<uint8_t> parity = rs_parity_rows(n, k);
 
   const HostBlock blocks[3] = {{plan.items.data(), plan.items.size() * sizeof(UpdateItem)},
                                {plan.byte_prefix.data(), plan.byte_prefix.size() * sizeof(int64_t)},
@@ -374,13 +363,13 @@ int nxec_rs_update_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_strip
     const UpdateItem *d_items = reinterpret_cast<const UpdateItem *>(d + off[0]);
     const int64_t *d_prefix = reinterpret_cast<const int64_t *>(d + off[1]);
     const uint32_t *d_tiles = reinterpret_cast<const uint32_t *>(d + off[2]);
-    const int m = n - k, passes = std::max(1, (m + kMaxRowsPerPass - 1) / kMaxRowsPerPass);
+    const int m = n - k, passes = row_passes(m);
     int rc = NXEC_OK;
     for (size_t r = 0; r < plan.rounds.size() && !rc; r++) {
       const UpdateRound &rd = plan.rounds[r];
       for (int p = 0; p < passes && !rc; p++) {
-        const int row0 = p * kMaxRowsPerPass, rows = std::min(kMaxRowsPerPass, m - row0);
-        const uint8_t *coef = parity + static_cast<size_t>(row0) * k;
+        const int row0 = p * kMaxRowsPerPass, rows = pass_rows(m, p);
+        const uint8_t *coef = parity.data() + static_cast<size_t>(row0) * k;
         const bool last = p == passes - 1;
         rc = launch_update_vec(k, rows, row0, coef, d_stripes, chunk_stride, d_items, d_tiles + rd.tile0, rd.ntiles,
                                last, rd.nupdates, static_cast<int>(r), p, ctx->num_cus, st);
@@ -407,7 +396,7 @@ int nxec_rs_scrub_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripe
   const bool work = len > 0 && nstripes > 0 && m > 0;
   if (work && !d_stripes) return set_error(NXEC_ERR_INVALID, "null stripe buffer");
   // chunk byte offsets inside a stripe stay 32-bit (the kernels' scalar address math)
-  if (work && (chunk_stride < 0 || static_cast<int64_t>(n - 1) * chunk_stride + len > (int64_t(1) << 32) - 1))
+  if (work && !stripe_fits32(n, chunk_stride, len))
     return set_error(NXEC_ERR_INVALID, "scrub: chunk offset out of range (chunks of a stripe must lie within 4 GiB)");
   if (nstripes == 0) return NXEC_OK;
   int rc = ensure_device(ctx->device);
@@ -416,9 +405,7 @@ int nxec_rs_scrub_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripe
   NXEC_HIP(hipMemsetAsync(d_status, 0xFF, static_cast<size_t>(nstripes) * sizeof(int32_t), st));  // CLEAN
   if (!work) return NXEC_OK;
 
-  std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
-  nxec_gf_gen_rs_matrix(enc.data(), n, k);  // rs.cc:26
-  const uint8_t *par = enc.data() + static_cast<size_t>(k) * k;
+  const std::vector<uint8_t> par = rs_parity_rows(n, k);
 
   ScrubArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -434,13 +421,10 @@ int nxec_rs_scrub_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripe
   const bool vec_ok = aligned16(d_stripes) && chunk_stride % 16 == 0 && stripe_stride % 16 == 0;
   const int64_t max_stripes = max_stripes_per_launch(len / 16);
   // detect: one pass per 4 parity rows, every pass flagging the same status word
-  for (int r0 = 0; r0 < m; r0 += kMaxRowsPerPass) {
-    const int pr = std::min(kMaxRowsPerPass, m - r0);
-    a.m.rows = pr;
-    for (int r = 0; r < kMaxRowsPerPass; r++) {
-      a.par_off[r] = r < pr ? static_cast<uint32_t>((k + r0 + r) * chunk_stride) : 0;
-      for (int j = 0; j < k; j++) a.m.coef[r * k + j] = r < pr ? par[static_cast<size_t>(r0 + r) * k + j] : 0;
-    }
+  for (int p = 0; p < row_passes(m); p++) {
+    a.m.rows = pass_coef(m, k, par.data(), p, a.m.coef);
+    for (int r = 0; r < kMaxRowsPerPass; r++)
+      a.par_off[r] = r < a.m.rows ? static_cast<uint32_t>((k + p * kMaxRowsPerPass + r) * chunk_stride) : 0;
     for (int64_t s0 = 0; s0 < nstripes; s0 += max_stripes) {
       ScrubArgs b = a;
       b.m.nstripes = std::min(max_stripes, nstripes - s0);
@@ -452,7 +436,7 @@ int nxec_rs_scrub_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_stripe
   if (!d_nbad && !(flags & NXEC_SCRUB_LOCATE)) return NXEC_OK;  // nothing left to count or locate
   // locate / heal: the stage reads the parity rows from device memory, uploaded once per (device, n, k)
   const uint8_t *d_coef = nullptr;
-  if ((rc = scrub_coef(ctx->device, n, k, par, &d_coef))) return rc;
+  if ((rc = scrub_coef(ctx->device, n, k, par.data(), &d_coef))) return rc;
   for (int64_t s0 = 0; s0 < nstripes; s0 += (int64_t(1) << 30)) {
     ScrubLocateArgs la{};
     la.base = d_stripes + s0 * stripe_stride;
@@ -508,11 +492,11 @@ int nxec_rs_decode_stripes_mixed(nxec_ctx_t *ctx, int n, int k, const unsigned c
   if (!alive && nstripes > 0) return set_error(NXEC_ERR_INVALID, "mixed decode: null alive map");
   if (out_chunk_stride < len || out_stripe_stride < static_cast<__int128>(k - 1) * out_chunk_stride + len)
     return set_error(NXEC_ERR_INVALID, "mixed decode: output strides smaller than the chunks");
-  // chunk byte offsets inside a stripe stay 32-bit (the kernels' scalar address math)
-  constexpr int64_t kOffMax = (int64_t(1) << 32) - 1;
+  // chunk byte offsets inside a stripe stay 32-bit (the kernels' scalar address math); this call has always refused a
+  // stride past the limit for a one-chunk stripe too, which the rule alone would let through
   if (len > 0 && nstripes > 0 &&
-      (chunk_stride > kOffMax || out_chunk_stride > kOffMax || static_cast<int64_t>(n - 1) * chunk_stride + len > kOffMax ||
-       static_cast<int64_t>(k - 1) * out_chunk_stride + len > kOffMax))
+      (chunk_stride > kStripeOffMax || out_chunk_stride > kStripeOffMax || !stripe_fits32(n, chunk_stride, len) ||
+       !stripe_fits32(k, out_chunk_stride, len)))
     return set_error(NXEC_ERR_INVALID, "mixed decode: chunk offset out of range (chunks of a stripe must lie within 4 GiB)");
   // the output must stay clear of the source: the kernel loads tile t+1 before it stores tile t
   if (len > 0 && nstripes > 0 && d_stripes && d_out) {
@@ -590,9 +574,7 @@ bool encode_md5_args(int n, int k, const unsigned char *data, int64_t data_cs, i
   for (int r = 0; r < p; r++)
     if (!chunk_off32(r, par_cs, len, &a.dst_off[r])) return false;
   if (!mul_md5_eligible(k, p, len, data, data_ss, a.src_off, parity, par_ss, a.dst_off)) return false;
-  std::vector<uint8_t> enc(static_cast<size_t>(n) * k);
-  nxec_gf_gen_rs_matrix(enc.data(), n, k);  // rs.cc:26
-  std::memcpy(a.coef, enc.data() + static_cast<size_t>(k) * k, static_cast<size_t>(p) * k);
+  std::memcpy(a.coef, rs_parity_rows(n, k).data(), static_cast<size_t>(p) * k);
   a.src = data;
   a.src_stripe_stride = data_ss;
   a.dst = parity;
@@ -622,8 +604,7 @@ int nxec_rs_encode_md5_stripes(nxec_ctx_t *ctx, int n, int k, unsigned char *d_s
   if (nstripes == 0) return NXEC_OK;
   MulMd5Args ea;
   // the parity chunks count from the stripe like the data chunks, as in the two-kernel path below
-  uint32_t last_off = 0;
-  if (chunk_off32(n - 1, chunk_stride, len, &last_off) &&
+  if (stripe_fits32(n, chunk_stride, len) &&
       encode_md5_args(n, k, d_stripes, chunk_stride, stripe_stride, d_stripes + int64_t(k) * chunk_stride, chunk_stride,
                       stripe_stride, d_digests, len, nstripes, ea)) {
     int rc = ensure_device(ctx->device);

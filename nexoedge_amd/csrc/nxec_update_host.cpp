@@ -47,7 +47,7 @@ int update_plan(int n, int k, int64_t cs, int64_t ss, int64_t len, int64_t nstri
   p = UpdatePlan{};
   if (live.empty()) return NXEC_OK;
   // chunk byte offsets inside a stripe stay 32-bit (the kernels' scalar address math)
-  if (static_cast<int64_t>(n - 1) * cs + len > (int64_t(1) << 32) - 1)
+  if (!stripe_fits32(n, cs, len))
     return set_error(NXEC_ERR_INVALID, "update: chunk offset out of range (chunks of a stripe must lie within 4 GiB)");
 
   // by stripe, then by first column: the order the interval colouring wants

@@ -1,10 +1,15 @@
 // The host rules that keep the fused multiply + MD5 kernels' 32-bit offsets
-// from wrapping (nxec_internal.h; no device and no libnxec: the three are
+// from wrapping (nxec_internal.h; no device and no libnxec: all are
 // inline): chunk_off32, the contract "(idx * stride) + len <= 2^32 - 1" of every
-// strided call; mul_md5_layout_ok, the eligibility the three fused call sites
-// share; mul_md5_group_cap, the stripes per workgroup that launch_mul_md5 may
-// use at a given stripe stride.
+// strided call, and stripe_fits32, the same rule for a whole stripe;
+// mul_md5_layout_ok, the eligibility the three fused call sites share;
+// mul_md5_group_cap, the stripes per workgroup that launch_mul_md5 may use at a
+// given stripe stride.  With them the other inline host helpers of that header:
+// row_passes / pass_rows / pass_coef, the split of a coefficient matrix into
+// passes of at most 4 rows.
 #include <cstdio>
+#include <cstring>
+#include <vector>
 
 #include "nxec.h"
 #include "nxec_internal.h"
@@ -32,6 +37,48 @@ int main() {
   CHECK(chunk_off32(0, G4, 16, &o) && o == 0);  // chunk 0 alone: the stride is never walked
   CHECK(!chunk_off32(-1, 16, 16, &o) && !chunk_off32(1, -16, 16, &o) && !chunk_off32(1, 16, -1, &o));
   CHECK(chunk_off32(0, 16, G4 - 1, &o) && !chunk_off32(0, 16, G4, &o));
+
+  // stripe_fits32(n, stride, len) == chunk_off32(n - 1, stride, len, ..): the rule for a whole stripe
+  CHECK(stripe_fits32(6, 858992638, 4105) && 5 * int64_t(858992638) + 4105 == G4 - 1);
+  CHECK(!stripe_fits32(6, 858992638, 4106));  // one byte more
+  CHECK(stripe_fits32(1, 16, G4 - 1) && !stripe_fits32(1, 16, G4) && !stripe_fits32(1, G4, G4));
+  CHECK(stripe_fits32(1, G4, 16));  // one chunk: the stride is never walked
+  CHECK(!stripe_fits32(6, -16, 16) && !stripe_fits32(6, 16, -1) && !stripe_fits32(0, 16, 16));
+  // (n - 1) * stride wraps int64 here: the hand-written forms of the rule computed it first (UBSan aborts on that)
+  CHECK(!stripe_fits32(255, int64_t(1) << 57, 4096) && !stripe_fits32(255, INT64_MAX, 1));
+  for (const int64_t nn : {1, 2, 6, 24, 255})
+    for (const int64_t st : {int64_t(0), int64_t(16), int64_t(858992638), G4 - 2, G4 - 1, G4, int64_t(1) << 57})
+      for (const int64_t ln : {int64_t(0), int64_t(1), int64_t(4105), int64_t(4106), G4 - 1, G4})
+        CHECK(stripe_fits32(nn, st, ln) == chunk_off32(nn - 1, st, ln, &o));
+
+  // row_passes / pass_rows / pass_coef: a rows x k matrix in passes of at most 4 rows, at least one pass
+  static_assert(kMaxRowsPerPass == 4, "the cases below count in fours");
+  for (const int k : {1, 19, NXEC_MAX_K}) {
+    for (const int rows : {0, 1, 4, 5, 8, 9}) {
+      std::vector<uint8_t> m(static_cast<size_t>(rows) * k);
+      for (size_t i = 0; i < m.size(); i++) m[i] = static_cast<uint8_t>(1 + i % 251);  // never zero
+      const int passes = row_passes(rows);
+      CHECK(passes == (rows == 0 ? 1 : (rows + 3) / 4));
+      int total = 0;
+      for (int p = 0; p < passes + 1; p++) {  // one pass past the end too: no rows, nothing read
+        // exactly the block: ASan guards both ends, and the block starts as 0xEE
+        std::vector<uint8_t> coef(static_cast<size_t>(kMaxRowsPerPass) * k, 0xEE);
+        const int pr = pass_coef(rows, k, rows ? m.data() : nullptr, p, coef.data());
+        CHECK(pr == pass_rows(rows, p) && pr == std::min(4, std::max(0, rows - 4 * p)));
+        CHECK(p < passes ? (pr > 0 || rows == 0) : pr == 0);
+        for (int r = 0; r < kMaxRowsPerPass; r++)
+          for (int j = 0; j < k; j++)
+            CHECK(coef[r * k + j] == (r < pr ? m[static_cast<size_t>(4 * p + r) * k + j] : 0));
+        total += pr;
+      }
+      CHECK(total == rows);
+      // inside a kernel-argument block of its full size, the bytes past 4 * k stay as they were
+      uint8_t block[kMaxRowsPerPass * (NXEC_MAX_K + 1)];
+      std::memset(block, 0xEE, sizeof block);
+      pass_coef(rows, k, rows ? m.data() : nullptr, 0, block);
+      for (size_t i = static_cast<size_t>(kMaxRowsPerPass) * k; i < sizeof block; i++) CHECK(block[i] == 0xEE);
+    }
+  }
 
   // mul_md5_layout_ok: RS(20,16) with data chunk 15 at 2^32 - 256 and 512-byte chunks is the layout the
   // fused encode used to take and wrap on; the same start with one 256-byte step less is not legal either

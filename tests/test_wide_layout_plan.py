@@ -131,6 +131,24 @@ def test_device_calls_refuse_one_byte_more_before_any_device_use(shape):
     assert b"4 GiB" in _lib.lib.nxec_last_error()
 
 
+@pytest.mark.parametrize("n,k", [(6, 4), (24, 21), (128, 124)])
+def test_a_stride_whose_product_overflows_int64_is_refused(n, k):
+    """chunk_stride = 2^57: (n-1) * chunk_stride is merely huge for the small codes and wraps a signed 64-bit product
+    for n = 128, to -2^57, which passes for a layout within 4 GiB.  The recover, the scrub and the update used to
+    multiply before they compared; all three refuse the stride by the 4 GiB rule, before the context or a buffer
+    is touched."""
+    cs, ln, fake = 1 << 57, 4096, ctypes.c_void_p(1)
+    assert (n - 1) * cs + ln > G4 - 1 and (n < 128 or (n - 1) * cs >= 1 << 63)
+    last_error = _lib.lib.nxec_last_error
+    assert update_plan(n, k, cs, ln) == (INVALID, (-7, -7, -7)) and b"4 GiB" in last_error()
+    assert update_call(fake, n, k, cs, ln) == INVALID and b"update" in last_error() and b"4 GiB" in last_error()
+    assert recover_mixed_call(fake, n, k, cs, ln) == (INVALID, [9, 9])
+    assert b"mixed recover" in last_error() and b"4 GiB" in last_error()
+    for flags in (0, nxec.SCRUB_LOCATE, nxec.SCRUB_REPAIR):
+        assert scrub_call(fake, n, k, cs, ln, flags) == INVALID
+        assert b"scrub" in last_error() and b"4 GiB" in last_error()
+
+
 @pytest.mark.skipif(nxec.device_count() > 0, reason="a GPU is visible")
 @pytest.mark.parametrize("shape", sorted(SHAPES))
 def test_device_calls_take_the_limit(shape):
