@@ -13,10 +13,12 @@ An instantiation is named by a tuple:
   ("k_mul_md5", k, hsrc)                     ("k_gather_md5", k, hsrc)
   ("k_files_md5", k, mask, tstore)           ("k_mul_mixed", k)
   ("k_decode_mixed", k)                      ("k_update_vec", r)
-k_mul_list, k_scrub_bytes, k_update_bytes and the plain MD5 kernels are not
-templates over k; their launches are recorded and checked per case but are not
-part of the set.  k_update_vec takes k at run time, but k sizes its LDS and the
-updated chunk's index picks the table, so group (h) still runs every k.
+k_mul_list, k_scrub_bytes and k_update_bytes are not templates over k; their
+launches are recorded and checked per case but are not part of the set.  The
+plain MD5 launches (k_md5: launch_md5, launch_md5_list) are not recorded at
+all; tests/digest_matrix.py covers that kernel by its results.  k_update_vec
+takes k at run time, but k sizes its LDS and the updated chunk's index picks
+the table, so group (h) still runs every k.
 
 The constants below mirror nexoedge_amd/csrc (the CPU test reads the sources
 and fails when one moves).

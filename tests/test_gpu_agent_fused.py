@@ -153,3 +153,116 @@ def test_agent_without_digests_zero_copy(gpu_ctx, in_kind, out_kind, cs):
     none) run the gather form of the multiply kernel over the same pointer
     tables -- mapped buffers in place, the others through the slot."""
     run_batch(gpu_ctx, SHAPES, cs, in_kind, out_kind, nreq=10, seed=cs + 7, with_md5=lambda r: False)
+
+
+# ----------------------------------------------------------------------------
+# The staged form with digests (H2D -> multiply -> k_md5 -> D2H): what a group
+# takes with more than kGatherMd5MaxK (16) inputs, more than kMaxRowsPerPass (4)
+# outputs, or with zero copy switched off (NXEC_HOST_DIRECT=0).
+
+def run_digest_batch(gpu_ctx, shapes, cs, in_kind, out_kind, nreq, seed, hash_inputs, batch_bytes=0,
+                     without_md5=lambda r: False):
+    """One nxec_agent_encode_batch call of `nreq` requests cycling through `shapes`; the requests of a shape
+    share its matrix, so they form one group and travel in batches of several.  Outputs are the first cs bytes
+    of larger sentinel-filled buffers and the digest arrays carry a sentinel row behind them.  Checks outputs
+    against the oracle, output and input digests against hashlib, and that nothing past cs or past the digests
+    was written.  Returns the call's launch record."""
+    rng = np.random.default_rng(seed)
+    arena = Arena()
+    mats = {sh: rng.integers(0, 256, size=(sh[1], sh[0]), dtype=np.uint8) for sh in dict.fromkeys(shapes)}
+    reqs, want, guards = [], [], []
+    try:
+        for r in range(nreq):
+            ni, no = shapes[r % len(shapes)]
+            ins = []
+            for j in range(ni):
+                a = make_buf(arena, in_kind, cs, r * 7 + j)
+                a[:] = rng.integers(0, 256, size=cs, dtype=np.uint8)
+                ins.append(a)
+            big = [make_buf(arena, out_kind, cs + 64, r * 5 + o) for o in range(no)]
+            for b in big:
+                b[:] = 0xEE
+            md5 = None if without_md5(r) else np.full((no + 1, 16), 0xEE, dtype=np.uint8)
+            md5_in = np.full((ni + 1, 16), 0xEE, dtype=np.uint8) if hash_inputs else None
+            reqs.append((mats[(ni, no)], ins, [b[:cs] for b in big], md5[:no] if md5 is not None else None,
+                         md5_in[:ni] if md5_in is not None else None))
+            want.append(oracle.matmul(mats[(ni, no)], [x.copy() for x in ins]))
+            guards.append((big, md5, md5_in))
+        nxec.launch_log(True)
+        try:
+            gpu_ctx.agent_encode_batch(reqs, cs, batch_bytes)
+            recs = nxec.launch_log_read()
+        finally:
+            nxec.launch_log(False)
+        for r, ((m, ins, outs, _, _), w, (big, md5, md5_in)) in enumerate(zip(reqs, want, guards)):
+            for o in range(m.shape[0]):
+                assert np.array_equal(outs[o], w[o]), (r, o)
+                assert (big[o][cs:] == 0xEE).all(), (r, o)  # nothing written past the chunk
+                if md5 is not None:
+                    assert md5[o].tobytes() == hashlib.md5(w[o].tobytes()).digest(), (r, o)
+            if md5 is not None:
+                assert (md5[-1] == 0xEE).all(), r
+            if md5_in is not None:
+                for j in range(m.shape[1]):
+                    assert md5_in[j].tobytes() == hashlib.md5(ins[j].tobytes()).digest(), (r, "input", j)
+                assert (md5_in[-1] == 0xEE).all(), r
+        return recs
+    finally:
+        arena.free()
+
+
+def gather_shapes(recs):
+    return [(r["k"], r["p"]) for r in recs if r["family"] == "k_gather_md5"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hash_inputs", [False, True])
+@pytest.mark.parametrize("cs", [1, 255, 256, 5000, 65536 + 16])
+def test_agent_staged_with_digests(gpu_ctx, cs, hash_inputs):
+    """Shapes past the fused kernel's limits (more than 16 inputs, more than 4 outputs, both): the staged form,
+    whose MD5 launch hashes the outputs alone or -- with md5_inputs -- two regions, the inputs' digests first
+    in a request's digest row and the outputs' behind them.  A request without an md5 pointer shares the batch
+    when the inputs are not hashed."""
+    for ni, no in [(17, 1), (20, 4), (4, 5), (4, 6), (20, 6)]:
+        recs = run_digest_batch(gpu_ctx, [(ni, no)], cs, "mixed", "mixed", nreq=5,
+                                seed=zlib.crc32(repr((ni, no, cs, hash_inputs)).encode()), hash_inputs=hash_inputs,
+                                without_md5=lambda r: not hash_inputs and r == 2)
+        fam = [r["family"] for r in recs]
+        assert "k_gather_md5" not in fam and any(f.startswith("k_mul_") for f in fam), ((ni, no), fam)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hash_inputs", [False, True])
+def test_agent_round_mixing_fused_and_staged_groups(gpu_ctx, hash_inputs):
+    """One call whose groups alternate between the fused form ((4, 1), (16, 4)) and the staged form ((17, 1),
+    (4, 5)), split into many batches: the three rotating slots are each handed from one form to the other."""
+    shapes = [(4, 1), (17, 1), (4, 5), (16, 4)]
+    cs, per_shape, batch_bytes = 8192, 6, 100000
+    # the staged groups alone: (ni + no) * cs exceeds half of batch_bytes for both, so one request per batch
+    assert all((ni + no) * cs > batch_bytes // 2 for ni, no in ((17, 1), (4, 5)))
+    recs = run_digest_batch(gpu_ctx, shapes, cs, "mixed", "mixed", nreq=per_shape * len(shapes), seed=4100 + hash_inputs,
+                            hash_inputs=hash_inputs, batch_bytes=batch_bytes)
+    gathered = gather_shapes(recs)
+    assert set(gathered) == {(4, 1), (16, 4)}, gathered  # the two narrow shapes only
+    staged = [r for r in recs if r["family"] != "k_gather_md5"]
+    assert {r["k"] for r in staged} == {17, 4} and all(r["family"].startswith("k_mul_") for r in staged), staged
+    assert len(gathered) + 2 * per_shape >= 7  # batches of the round: every slot is used at least twice
+    # groups run in key order (4, 1), (4, 5), (16, 4), (17, 1): fused, staged, fused, staged
+    form = ["F" if r["family"] == "k_gather_md5" else "S" for r in recs]
+    runs = [f for i, f in enumerate(form) if i == 0 or form[i - 1] != f]
+    assert runs == ["F", "S", "F", "S"], runs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hash_inputs", [False, True])
+@pytest.mark.parametrize("kind", ["arena", "pageable"])
+@pytest.mark.parametrize("cs", [5000, 65536])
+def test_agent_staged_when_zero_copy_is_off(gpu_ctx, monkeypatch, cs, kind, hash_inputs):
+    """NXEC_HOST_DIRECT=0 (a deployment setting, read at every call): every shape takes the staged form, and
+    outputs and digests come back by a plain device-to-host copy instead of the copy kernel."""
+    monkeypatch.setenv("NXEC_HOST_DIRECT", "0")
+    for ni_no in SHAPES:
+        recs = run_digest_batch(gpu_ctx, [ni_no], cs, kind, kind, nreq=5,
+                                seed=zlib.crc32(repr((ni_no, cs, kind, hash_inputs)).encode()), hash_inputs=hash_inputs)
+        fam = [r["family"] for r in recs]
+        assert "k_gather_md5" not in fam and any(f.startswith("k_mul_") for f in fam), (ni_no, fam)

@@ -97,6 +97,39 @@ def test_encode_host_md5_outputs_only_and_empty(gpu_ctx, placement):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("placement", ["gpu"], indirect=True)
+@pytest.mark.parametrize("n,k", [(24, 20), (10, 4), (22, 17)])
+@pytest.mark.parametrize("cs", [1000, 65537])
+def test_encode_host_md5_wide_codes_take_the_staged_form(gpu_ctx, placement, n, k, cs):
+    """RSCode::encode of a code wider than the fused kernel (k > 16, n - k > 4, or both): the call goes to the
+    agent service as one staged request with the inputs hashed -- multiply, then one MD5 launch over two
+    regions.  Parity against the oracle, all n digests against hashlib, no k_gather_md5 launch."""
+    rng = np.random.default_rng(n * 1000 + k + cs)
+    arena = Arena()
+    try:
+        data = [make_buf(arena, "mixed", cs, j) for j in range(k)]
+        for d in data:
+            d[:] = rng.integers(0, 256, size=cs, dtype=np.uint8)
+        outs = [make_buf(arena, "mixed", cs, k + r) for r in range(n - k)]
+        enc = nxec.gen_rs_matrix(n, k)[k:]
+        nxec.launch_log(True)
+        try:
+            _, md_in, md_out = nxec.encode_host_md5(enc, data, outs)
+            fam = [r["family"] for r in nxec.launch_log_read()]
+        finally:
+            nxec.launch_log(False)
+        assert "k_gather_md5" not in fam and any(f.startswith("k_mul_") for f in fam), fam
+        want = oracle.rs_encode(n, k, np.concatenate(data), cs)
+        for r in range(n - k):
+            assert np.array_equal(outs[r], want[k + r]), f"parity {r}"
+            assert np.array_equal(md_out[r], md5(want[k + r])), f"parity digest {r}"
+        for j in range(k):
+            assert np.array_equal(md_in[j], md5(data[j])), f"data digest {j}"
+    finally:
+        arena.free()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("placement", ["gpu", "auto"], indirect=True)
 def test_encode_host_md5_concurrent_callers_share_rounds(gpu_ctx, placement):
     """16 threads each encoding RS(10,4) stripes with digests at once (the
